@@ -15,7 +15,13 @@ equal --gpus. Systems are sharded by global id with no data-path collective (wea
 scaling); the single exchange is one RCCL all-reduce of the per-transaction histograms
 after the timed region.
 
-The headline line also carries `contention` (BASELINE configs[3], its own timed steps),
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline figure
+needs: it generates the traces, runs W untimed and K timed steps, writes --dump-outputs DIR
+(what the last timed step computed, as .npy files) and prints the line: `metric`, `value`,
+`ms_per_step`, the roofline fraction from the timed launches and dash_run's own counters.
+Everything below is behind --full.
+
+With --full the headline line also carries `contention` (BASELINE configs[3], its own timed steps),
 `cpu_baseline` (the reference itself, assignment.c + the SURVEY §8(d) benchmark patch,
 one instance per host core = BASELINE.md mode (A)) and `cpu_port` (the oracle restatement
 on the same host). Every line certifies its own results at any GPU count (`golden`, round 6):
@@ -966,10 +972,87 @@ def vector_pipe(prof, wave_rounds):
             "(tools/micro/valu_ops), static mix from profiles/isa_table.json"}
 
 
-def run_kind(dash, args, kind_name, M, sys_base, world, dev, steps, tier_flag, sampler=None):
+DUMP_LIMIT = 64 << 20  # bytes of --dump-outputs files per rank
+DUMP_SAMPLE_SEED = 0xD0D0  # fixed: the same systems are sampled in every run of the same size
+
+
+def dump_outputs(eng, stats, out_dir, rank=0):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float64 .npy
+    files (rank 0: <name>.npy, rank r > 0: <name>.rank<r>.npy). `stats` is dash_run's return (the
+    per-type histogram and the counters that do not depend on timing); the per-system results of
+    dash_read_results follow: the 64-bit state digest as its two 32-bit halves (exact in float64),
+    the round count and the error bits. Above DUMP_LIMIT bytes the per-system arrays are a fixed,
+    seeded, sorted sample of the systems, whose ids are written beside them."""
+    import numpy as np
+    out = pathlib.Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    d, r, e = eng.read_results()
+    n = len(d)
+    keep = (DUMP_LIMIT - 4096) // (5 * 8)  # five float64 per system; 4 KB for the headers and the small arrays
+    ids = np.arange(n, dtype=np.int64)
+    if n > keep:
+        ids = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=keep, replace=False))
+    arrays = {"hist": np.array(stats["hist"], dtype=np.float64),
+              "counters": np.array([stats[k] for k in ("instructions", "rounds_total", "rounds_max", "systems",
+                                                       "err_systems", "err_bits", "dropped", "max_depth")],
+                                   dtype=np.float64),
+              "system_id": ids.astype(np.float64),
+              "digest_lo": (d[ids] & np.uint64(0xFFFFFFFF)).astype(np.float64),
+              "digest_hi": (d[ids] >> np.uint64(32)).astype(np.float64),
+              "rounds": r[ids].astype(np.float64),
+              "errors": e[ids].astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(out / (f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), a)
+
+
+def plain_run(dash, args, M, sys_base, rank, world, dev, tier_flag):
+    """The run without --full: set up, warm up, time the steps, write --dump-outputs, print the
+    line. Its one collective is the MAX of the timed region and the SUM of dash_run's counters."""
+    import torch
+    import torch.distributed as dist
+    kind = {"uniform": dash.GEN_UNIFORM, "contention": dash.GEN_CONTENTION,
+            "locality": dash.GEN_LOCALITY}[args.kind]
+    locality = int(round(args.locality * 65536)) if args.kind == "locality" else 0
+    eng = dash.Engine(M, num_procs=8, cache_size=args.cache_size, max_instr=args.len,
+                      device=dev, flags=tier_flag)
+    try:
+        eng.generate(args.seed, args.len, kind=kind, locality=locality, sys_base=sys_base)
+        elapsed, stats, kernel_ms = timed_headline(eng, args, world, dev)
+        if args.dump_outputs:
+            dump_outputs(eng, stats, args.dump_outputs, rank)
+    finally:
+        eng.close()
+    vec = stats["hist"] + [stats["instructions"], stats["rounds_total"], stats["err_systems"], stats["dropped"]]
+    elapsed, totals = reduce_totals(elapsed, vec, torch.device("cuda", dev), world)
+    if dist.is_initialized():
+        dist.destroy_process_group()
+    if rank != 0:
+        return
+    avg_kernel_s = sum(kernel_ms) / len(kernel_ms) / 1e3
+    line = {"metric": "simulated instr/sec (whole node), 8-core DASH systems; % HBM roofline",
+            "value": sig(world * M * 8 * args.len * args.steps / elapsed, 5), "unit": "instr/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": sig(elapsed / args.steps * 1e3, 5), "higher_is_better": True, "scaling": "weak",
+            "dtype": "u8",
+            "data": "synthetic (on-device counter-based generator, seed keyed by global system id)",
+            "config": {"workload": f"{M} systems/GPU x 8 nodes x {args.len} {args.kind} RD/WR per node, "
+                                   f"CACHE_SIZE={args.cache_size}",
+                       "parallelism": f"systems sharded over {world} GPU(s)"},
+            "kernel_ms_avg": sig(avg_kernel_s * 1e3, 5),
+            "roofline": compact_roofline(roofline(M, args.len, avg_kernel_s, None)),
+            "totals": {"hist": totals[:13], "instructions_per_step": totals[13], "rounds_total": totals[14],
+                       "err_systems": totals[15], "dropped": totals[16]},
+            "full": False,
+            "note": "headline only; --full adds the golden checks, contention, the sweep, the CPU baselines, "
+                    "the box probes and the side file"}
+    print(json.dumps(line, separators=(",", ":")), flush=True)
+
+
+def run_kind(dash, args, kind_name, M, sys_base, world, dev, steps, tier_flag, sampler=None, dump_dir=None,
+             rank=0):
     """One workload (uniform / contention / locality): generate on the device, time it (the
     optional ClockSampler samples the clock meanwhile), all-reduce the totals; returns
-    (elapsed, totals, stats, kernel_ms)."""
+    (elapsed, totals, stats, kernel_ms). `dump_dir`: --dump-outputs of the last timed step."""
     import torch
     kind = {"uniform": dash.GEN_UNIFORM, "contention": dash.GEN_CONTENTION,
             "locality": dash.GEN_LOCALITY}[kind_name]
@@ -985,6 +1068,8 @@ def run_kind(dash, args, kind_name, M, sys_base, world, dev, steps, tier_flag, s
                 elapsed, stats, kernel_ms = timed_headline(eng, a, world, dev)
         else:
             elapsed, stats, kernel_ms = timed_headline(eng, a, world, dev)
+        if dump_dir:
+            dump_outputs(eng, stats, dump_dir, rank)
         # a checksum of the per-system state digests (sums of their 32-bit
         # halves: order-free, so identical for any GPU count), read back after the timed region,
         # with this rank's golden checks (its slice, its sampled ids)
@@ -1209,6 +1294,17 @@ def main():
                     help="ranks (one per GPU); without torchrun bench.py starts them itself")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline's timed steps: the golden checks of its results, the contention "
+                         "workload, the configs[4] grid, the event-log and seeded-schedule rows, the CPU baselines, "
+                         "the box probes and the committed PMC figures, with the full record in the --detail side "
+                         "file. Without it the run sets up, warms up, times --steps steps and prints the line; "
+                         "--contention-steps, --line-sweep, --line-next, --cpu-*, --ref-*, --no-cpu-baseline and "
+                         "--detail act only with --full")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64): "
+                         "dash_run's histogram and counters, and the per-system digests, rounds and error bits "
+                         "(a fixed seeded sample of the systems above 64 MB)")
     ap.add_argument("--systems", type=int, default=1 << 20, help="systems per GPU")
     ap.add_argument("--len", type=int, default=4096, help="instructions per node")
     ap.add_argument("--cache-size", type=int, default=4)
@@ -1284,6 +1380,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(launch_ranks(args))
     rank = int(os.environ.get("RANK", "0"))
@@ -1346,11 +1444,13 @@ def main():
 
     tier_flag = {0: 0, 32: dash.TIER_FROM_32, 256: dash.TIER_FROM_256}[args.first_depth]
     sys_base, M = shard(rank, world, args.systems)
+    if not args.full:
+        return plain_run(dash, args, M, sys_base, rank, world, dev, tier_flag)
     probe0 = box_probe(dash, dev)
     pdev = probe0.get("_dev") or {}
     sampler = ClockSampler(sysfs_dev_path(pdev["pci_domain"], pdev["pci_bus"])) if pdev else None
     elapsed, totals, stats, kernel_ms, slice_ok = run_kind(dash, args, args.kind, M, sys_base, world, dev,
-                                                 args.steps, tier_flag, sampler)
+                                                           args.steps, tier_flag, sampler, args.dump_outputs, rank)
     probe1 = box_probe(dash, dev)
     instr_per_step = world * M * 8 * args.len
     value = instr_per_step * args.steps / elapsed

@@ -141,13 +141,17 @@ def test_sig_keeps_types():
 
 
 def test_oversized_line_drops_summaries_not_the_headline(capsys, tmp_path, monkeypatch):
+    # the side file is named relative to the repo root, as in a bench run: the line's length must not
+    # depend on where pytest puts its temporary directories
+    monkeypatch.setattr(bench, "ROOT", tmp_path)
     monkeypatch.setattr(bench, "LINE_BUDGET", 2500)
-    bench.emit(synthetic_detail(8), str(tmp_path / "d.json"))
+    bench.emit(synthetic_detail(8), "d.json")
     line = json.loads(capsys.readouterr().out)
     assert {"value", "roofline", "cpu_baseline", "sweep"} <= set(line)
+    assert line["detail"] == "d.json" and (tmp_path / "d.json").exists()
     # a budget the sweep rows cannot fit: they stay in the side file, the line says so and still fits
     monkeypatch.setattr(bench, "LINE_BUDGET", 1800)
-    bench.emit(synthetic_detail(8), str(tmp_path / "d.json"))
+    bench.emit(synthetic_detail(8), "d.json")
     out = capsys.readouterr().out
     line = json.loads(out)
     assert len(out.strip()) <= 1800 and line["sweep"]["rows"] == 25 and "sweep" in line["dropped_for_size"]

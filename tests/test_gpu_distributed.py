@@ -14,7 +14,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = pathlib.Path(__file__).resolve().parent.parent
-ARGS = ["--systems", "2048", "--len", "4096", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"]
+ARGS = ["--systems", "2048", "--len", "4096", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"]
+# --full: the totals, golden checks, contention, sweep and CPU legs these tests read are behind it;
 # the torchrun rehearsal keeps the headline workload only
 
 
@@ -129,7 +130,7 @@ def test_two_rank_line_sweep_matches_one_process():
     N-GPU runs produce it at full size: every point's totals (all-reduced per point) equal one
     process running all the systems, and `value` counts both ranks' instructions."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    small = ["--len", "256", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--contention-steps", "0",
+    small = ["--len", "256", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--contention-steps", "0",
              "--line-sweep", "on", "--line-sweep-warmup", "0"]
     two = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
                           "--systems", "512"] + small, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
@@ -157,7 +158,7 @@ def test_four_ranks_line_is_the_driver_shape():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     # 4096 instructions per node: the length the golden fixtures hold, so every rank checks its
     # sampled ids (tests/golden/rank_samples.json) in every workload
-    small = ["--len", "4096", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--contention-steps", "1",
+    small = ["--len", "4096", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--contention-steps", "1",
              "--line-sweep", "on", "--line-sweep-warmup", "0"]
     four = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "4", "--dist-backend", "gloo",
                            "--systems", "256"] + small, capture_output=True, text=True, timeout=400, env=env, cwd=ROOT)
@@ -188,7 +189,7 @@ def test_eight_ranks_line_certifies_itself():
     systems per rank, the golden fixtures' 4096 instructions, the sweep in the line): all eight ranks
     hold sampled ids in all 27 workloads and none differs from the oracle; the line fits 4 KB."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    small = ["--len", "4096", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--contention-steps", "1",
+    small = ["--len", "4096", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--contention-steps", "1",
              "--line-sweep", "on", "--line-sweep-warmup", "0", "--systems", "256"]
     eight = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "8", "--dist-backend", "gloo"] + small,
                            capture_output=True, text=True, timeout=500, env=env, cwd=ROOT)

@@ -62,7 +62,7 @@ def test_headline_line_carries_the_sweep():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--systems", str(GOLD["systems"]),
                         "--len", str(GOLD["instr_per_node"]), "--seed", str(GOLD["seed"]), "--steps", "1",
-                        "--warmup", "0", "--contention-steps", "0", "--line-sweep", "on", "--cpu-seconds", "0.2",
+                        "--warmup", "0", "--full", "--contention-steps", "0", "--line-sweep", "on", "--cpu-seconds", "0.2",
                         "--ref-instances", "2", "--line-next", "on", "--next-event-systems", "256"],
                        capture_output=True, text=True, timeout=400, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -11,10 +11,10 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
   || { tail -20 "$OUT/tests.log"; exit 1; }
 tail -1 "$OUT/tests.log"
 step bench "(headline line: uniform + contention + CPU baselines)"
-timeout -k 10 400 python3 bench.py --steps 10 --warmup 2 > "$OUT/bench_uniform.json" 2> "$OUT/bench_uniform.err" || exit 1
+timeout -k 10 400 python3 bench.py --steps 10 --warmup 2 --full > "$OUT/bench_uniform.json" 2> "$OUT/bench_uniform.err" || exit 1
 step kernel trace
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- \
-    python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --contention-steps 2 > "$OUT/trace.log" 2>&1 || exit 1
+    python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --contention-steps 2 > "$OUT/trace.log" 2>&1 || exit 1
 step kernel trace, uniform launches only "(the headline kernel's own average)"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_uniform" -o run -- \
     python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --contention-steps 0 > "$OUT/trace_uniform.log" 2>&1 || exit 1
@@ -22,7 +22,7 @@ pmc() {  # kind name counters...
   local kind=$1 name=$2; shift 2
   step pmc "$kind" "$name"
   timeout -s KILL 150 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d "$OUT/pmc_$kind/$name" -o run -- \
-      python3 bench.py --kind "$kind" --steps 1 --warmup 0 --no-cpu-baseline --contention-steps 0 > "$OUT/pmc_$kind/$name.log" 2>&1 \
+      python3 bench.py --full --kind "$kind" --steps 1 --warmup 0 --no-cpu-baseline --contention-steps 0 > "$OUT/pmc_$kind/$name.log" 2>&1 \
       || { echo "pmc $name failed"; exit 1; }
 }
 for kind in uniform contention; do

@@ -9,7 +9,7 @@ TAG=$1; OUT=gpurun_out/ev_$TAG; mkdir -p "$OUT"; export TMPDIR=/tmp
 step() { echo "[$(date +%T)] $*"; }
 if [ -z "${SKIP_BENCH:-}" ]; then
   step bench "(the driver's command)"
-  timeout -k 10 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 1
+  timeout -k 10 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 1
 fi
 step kernel trace, uniform launches only
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_uniform" -o run -- \
@@ -18,7 +18,7 @@ pmc() {  # kind name counters...
   local kind=$1 name=$2; shift 2
   step pmc "$kind" "$name"
   timeout -s KILL 150 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d "$OUT/pmc_$kind/$name" -o run -- \
-      python3 bench.py --kind "$kind" --steps 1 --warmup 0 --no-cpu-baseline --contention-steps 0 --line-sweep off --line-next off \
+      python3 bench.py --full --kind "$kind" --steps 1 --warmup 0 --no-cpu-baseline --contention-steps 0 --line-sweep off --line-next off \
       > "$OUT/pmc_$kind/$name.log" 2>&1 || { echo "pmc $name failed"; exit 1; }
 }
 for kind in ${PMC_KINDS:-uniform contention}; do

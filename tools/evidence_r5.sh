@@ -14,13 +14,13 @@ if [ -z "${SKIP_TESTS:-}" ]; then
   timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.txt" 2>&1 || exit 1
 fi
 step bench "(the driver's command)"
-timeout -k 10 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 1
+timeout -k 10 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 1
 cp gpurun_out/bench_detail.json "$OUT/bench_detail.json"
 wc -c "$OUT/bench.json" "$OUT/bench.err"
 if [ -z "${SKIP_TRACE:-}" ]; then
   step kernel trace, uniform launches only
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_uniform" -o run -- \
-      python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --contention-steps 0 --line-sweep off --line-next off \
+      python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --contention-steps 0 --line-sweep off --line-next off \
       --detail "$OUT/trace_uniform_detail.json" > "$OUT/trace_uniform.log" 2>&1 || exit 1
 fi
 step evidence-done

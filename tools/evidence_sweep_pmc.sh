@@ -18,7 +18,7 @@ for pt in $POINTS; do
     local name=$1; shift
     step "$pt pass $name"
     timeout -s KILL 150 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d "$D/$name" -o run -- \
-        python3 bench.py $ARGS --steps 1 --warmup 0 \
+        python3 bench.py --full $ARGS --steps 1 --warmup 0 \
         --no-cpu-baseline --contention-steps 0 --line-sweep off --line-next off --detail "$D/$name.detail.json" \
         > "$D/$name.log" 2>&1 || { echo "pass $name failed"; exit 1; }
   }

@@ -4,6 +4,6 @@
 # its whole slice against tests/golden/full_slices.json. Usage (through gpurun): tools/four_rank_full.sh TAG
 set -uo pipefail
 OUT=gpurun_out/$1; mkdir -p "$OUT"; export TMPDIR=/tmp
-timeout -k 10 1000 python3 bench.py --gpus 4 --dist-backend gloo --steps 3 --warmup 1 \
+timeout -k 10 1000 python3 bench.py --gpus 4 --dist-backend gloo --steps 3 --warmup 1 --full \
     --detail "$OUT/bench_detail.json" > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "four-rank bench failed"; exit 1; }
 wc -c "$OUT/bench.json" "$OUT/bench.err"

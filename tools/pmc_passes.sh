@@ -3,7 +3,7 @@
 # under its own time limit). Usage: tools/pmc_passes.sh TAG [bench args]
 set -uo pipefail
 TAG=${1:-pmc}; shift || true
-ARGS=${*:-"--systems 131072 --steps 1 --warmup 0 --no-cpu-baseline"}
+ARGS=${*:-"--full --systems 131072 --steps 1 --warmup 0 --no-cpu-baseline"}
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp

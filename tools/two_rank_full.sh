@@ -5,6 +5,6 @@
 # ranks' sampled ids). Usage (through gpurun): tools/two_rank_full.sh TAG -> gpurun_out/TAG/
 set -uo pipefail
 OUT=gpurun_out/$1; mkdir -p "$OUT"; export TMPDIR=/tmp
-timeout -k 10 1000 python3 bench.py --gpus 2 --dist-backend gloo --steps 3 --warmup 1 \
+timeout -k 10 1000 python3 bench.py --gpus 2 --dist-backend gloo --steps 3 --warmup 1 --full \
     --detail "$OUT/bench_detail.json" > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "two-rank bench failed"; exit 1; }
 wc -c "$OUT/bench.json" "$OUT/bench.err"
