@@ -58,6 +58,24 @@ def state_arrays(nodes, N, CS):
     return out
 
 
+def check_stats(stats, results):
+    """Every dash_stats field of a run against the oracle's per-system results (queue capacity
+    256): the totals, and the fields a system abandoned at a shallower queue depth must not
+    touch (errors, drops, maximum depth, longest run)."""
+    hist_total = np.zeros(13, dtype=np.uint64)
+    for res in results:
+        hist_total += np.array(list(res.hist), dtype=np.uint64)
+    assert stats["hist"] == hist_total.tolist()
+    assert stats["rounds_total"] == sum(res.rounds for res in results)
+    assert stats["systems"] == len(results)
+    assert stats["instructions"] == sum(res.instructions for res in results)
+    assert stats["err_systems"] == sum(res.errors != 0 for res in results)
+    assert stats["err_bits"] == int(np.bitwise_or.reduce([res.errors for res in results] or [0]))
+    assert stats["dropped"] == sum(res.dropped for res in results)
+    assert stats["max_depth"] == max([res.max_depth for res in results] or [0])
+    assert stats["rounds_max"] == max([res.rounds for res in results] or [0])
+
+
 def check_batch(dash, packed, lens, N, CS, max_rounds=0, flags=0, seed=0, sched=None):
     nsys = packed.shape[0]
     with dash.Engine(nsys, num_procs=N, cache_size=CS, max_instr=packed.shape[2], keep_state=True,
@@ -67,9 +85,7 @@ def check_batch(dash, packed, lens, N, CS, max_rounds=0, flags=0, seed=0, sched=
         eng.load_traces(packed, lens)
         stats = eng.run()
         dig, rnd, err = eng.read_results()
-        hist_total = np.zeros(13, dtype=np.uint64)
-        rounds_total = 0
-        instr_total = 0
+        results = []
         for s in range(nsys):
             res = run_system(packed[s], lens[s], num_procs=N, cache_size=CS, ring_depth=256,
                              max_rounds=max_rounds or (1024 + 256 * packed.shape[2]), arb_seed=seed,
@@ -80,15 +96,10 @@ def check_batch(dash, packed, lens, N, CS, max_rounds=0, flags=0, seed=0, sched=
             assert int(err[s]) == res.errors, f"system {s} errors"
             assert int(dig[s]) == res.digest, f"system {s} digest"
             assert eng.read_hist(s).tolist() == list(res.hist), f"system {s} hist"
-            hist_total += np.array(list(res.hist), dtype=np.uint64)
-            rounds_total += res.rounds
-            instr_total += res.instructions
-        assert stats["hist"] == hist_total.tolist()
-        assert stats["rounds_total"] == rounds_total
-        assert stats["systems"] == nsys
-        assert stats["instructions"] == instr_total
+            results.append(res)
+        check_stats(stats, results)
         if not max_rounds:
-            assert instr_total == int(lens.sum())
+            assert stats["instructions"] == int(lens.sum())
     return stats
 
 
