@@ -255,6 +255,60 @@ int dash_load_dir(dash_t *h, const char *dir, uint64_t sys);
 /* Bulk ingest: system k = trace directory dirs[k] (same rules as dash_load_dir, ref
    :822-850; parsed on host threads, no "initialized" lines); n == cfg.num_systems. */
 int dash_load_dirs(dash_t *h, const char *const *dirs, uint64_t n);
+/* The same parse applied to a byte buffer (csrc/dash_text.c states the rules once): the
+   return code, *len and out[0..*len) equal those of dash_parse_core_file on a file holding
+   these bytes. Only the first 19 * max_instr bytes can matter. */
+int dash_parse_core_text(const char *text, size_t length, uint32_t num_procs, uint32_t max_instr,
+                         uint16_t *out, uint32_t *len);
+/* Gathers trace text without parsing it: at most 19 * max_instr bytes of each
+   <dirs[k]>/core_<t>.txt (t < num_procs; directories resolved by dash_resolve_dir), back to
+   back into buf, each file starting on a 16-byte boundary; file f = k * num_procs + t is
+   buf[offsets[f] .. offsets[f] + lengths[f]). *need = the bytes buf must hold; buf == NULL
+   measures only (offsets / lengths, when given, are still filled). DASH_EINVAL when cap <
+   *need; DASH_EIO on a missing file, after dash_parse_core_file's stderr line (ref :827). */
+int dash_read_dirs_text(const char *const *dirs, uint64_t n, uint32_t num_procs,
+                        uint32_t max_instr, char *buf, uint64_t cap, uint64_t *offsets,
+                        uint32_t *lengths, uint64_t *need);
+
+/* ---- device-side text ingest (libdash.so, HIP; csrc/dash_ingest.hip) ---- */
+/* Bytes per tile of the device parser (256 lanes x 16 bytes); exported so that tests can
+   place features on tile edges. */
+#define DASH_TEXT_TILE 4096
+/* Parses num_files == num_systems * num_procs trace texts on the device, straight into the
+   simulator's layout: file f = sys * num_procs + node is text[offsets[f] .. offsets[f] +
+   lengths[f]) (host pointers, any alignment; the slab is copied up to the largest offset +
+   length). Rules and results are those of dash_parse_core_text with the handle's num_procs and
+   max_instr. On success the handle is loaded exactly as dash_load_traces would have left it
+   for the same words. On failure the lowest failing file decides: its DASH_EPARSE or
+   DASH_EADDR is returned, dash_last_error names system, node and record, dash_ingest_info
+   gives the same as numbers -- and, unlike dash_load_dirs (which parses on the host and
+   leaves the device untouched), the handle is then NOT loaded: the device buffer was written
+   in place, so dash_run gives DASH_ESTATE until a load succeeds. */
+int dash_load_text(dash_t *h, const char *text, const uint64_t *offsets, const uint32_t *lengths,
+                   uint64_t num_files);
+/* dash_load_dirs with the parse on the device: host threads (at most 16, as dash_load_dirs
+   sizes them) only read the files' bytes into two pinned slabs, each holding a whole number of
+   files; a slab is copied and parsed while the other is being read. Same results as
+   dash_load_dirs on accepted input. Failure as dash_load_text, with DASH_EIO for a file the
+   reader could not open; the lowest failing file index wins whichever stage found it. */
+int dash_load_dirs_device(dash_t *h, const char *const *dirs, uint64_t n);
+/* The inverse of dash_load_traces: lens[sys * num_procs + node], and words [0, len) of every
+   row into packed[(sys * num_procs + node) * stride ..] (the rest of a row is zeroed), read
+   back from the device layout. stride >= the longest trace, else DASH_EINVAL. */
+int dash_read_traces(dash_t *h, uint16_t *packed, uint64_t stride, uint32_t *lens);
+/* The last dash_load_text / dash_load_dirs_device call of the handle. rc: its return code;
+   for DASH_EIO / DASH_EPARSE / DASH_EADDR, file = the failing file index (system * num_procs +
+   node) and record = the failing record, 1-based (0 for DASH_EIO). text_bytes: bytes copied to
+   the device. read_ms: host time spent reading files (wall clock of the reader phases);
+   copy_ms and parse_ms: H2D copies and the parse kernel, by device events. */
+typedef struct dash_ingest_report {
+    int32_t rc;
+    uint32_t record;
+    uint64_t file;
+    uint64_t text_bytes;
+    double read_ms, copy_ms, parse_ms;
+} dash_ingest_report;
+int dash_ingest_info(const dash_t *h, dash_ingest_report *out);
 /* Bulk emission: one system's printProcessorState files (ref :853-905) into out_dir
    (created if missing; needs DASH_KEEP_STATE), and a text file with one line
    "system digest(hex) rounds errors(hex)" for every system. */

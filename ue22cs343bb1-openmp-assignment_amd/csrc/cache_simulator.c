@@ -26,6 +26,7 @@
  *
  * Bulk modes (one GPU batch, many systems; dumps go to OUT_DIR/<k>/):
  *   --batch LIST        system k = the k-th trace directory listed in LIST (one per line)
+ *   --device-ingest     with --batch: parse the trace text on the GPU (dash_load_dirs_device)
  *   --synthetic COUNT   COUNT generated systems: --len L (4096) --kind uniform|contention|
  *                       locality --locality P (0.5) --seed S (0x5EED) --dump K[,K...]
  *   --digests FILE      "system digest rounds errors" for every system
@@ -193,6 +194,7 @@ typedef struct {
     unsigned long long seed, sched;
     int dev, show;
     const char *out, *digests, *dump;
+    int device_ingest;
 } bulk_opts;
 
 static void print_stats(const dash_stats *st);
@@ -246,7 +248,9 @@ static int run_batch_list(const char *list, const bulk_opts *o) {
     dash_t *h = NULL;
     dash_stats st;
     int rc = n ? dash_create(&cfg, &h) : DASH_EINVAL;
-    if (rc == DASH_OK && (rc = dash_load_dirs(h, (const char *const *)dirs, n)) == DASH_OK &&
+    if (rc == DASH_OK &&
+        (rc = o->device_ingest ? dash_load_dirs_device(h, (const char *const *)dirs, n)
+                               : dash_load_dirs(h, (const char *const *)dirs, n)) == DASH_OK &&
         (rc = dash_run(h, &st)) == DASH_OK)
         rc = finish_bulk(h, o, &st, n, 1);
     else if (h)
@@ -287,7 +291,7 @@ static int run_synthetic(uint64_t count, const bulk_opts *o) {
 
 int main(int argc, char *argv[]) {
     unsigned n = 4, cs = 4, m = 32;
-    int dev = 0, show = 0, dbg_instr = 0, dbg_msg = 0, n_given = 0;
+    int dev = 0, show = 0, dbg_instr = 0, dbg_msg = 0, n_given = 0, device_ingest = 0;
     const char *out = ".", *dir = NULL, *batch = NULL, *digests = NULL, *dump = NULL, *rounds_file = NULL,
                *micro_file = NULL;
     unsigned long long synth = 0, seed = 0x5EED, sched = 0;
@@ -303,6 +307,7 @@ int main(int argc, char *argv[]) {
         else if (!strcmp(argv[i], "--debug-instr")) dbg_instr = 1;
         else if (!strcmp(argv[i], "--debug-msg")) dbg_msg = 1;
         else if (!strcmp(argv[i], "--batch") && i + 1 < argc) batch = argv[++i];
+        else if (!strcmp(argv[i], "--device-ingest")) device_ingest = 1;
         else if (!strcmp(argv[i], "--synthetic") && i + 1 < argc) synth = strtoull(argv[++i], NULL, 0);
         else if (!strcmp(argv[i], "--digests") && i + 1 < argc) digests = argv[++i];
         else if (!strcmp(argv[i], "--dump") && i + 1 < argc) dump = argv[++i];
@@ -321,7 +326,8 @@ int main(int argc, char *argv[]) {
     }
     if (batch || synth) {
         if (synth && !n_given) n = 8; /* synthetic systems default to 8 nodes (BASELINE configs) */
-        bulk_opts o = {n, cs, m, len, kind, (unsigned)(loc * 65536.0), seed, sched, dev, show, out, digests, dump};
+        bulk_opts o = {n, cs, m, len, kind, (unsigned)(loc * 65536.0), seed, sched, dev, show, out, digests, dump,
+                       device_ingest};
         if (o.locality > 65536u) o.locality = 65536u;
         int rc = batch ? run_batch_list(batch, &o) : run_synthetic(synth, &o);
         return rc == DASH_OK ? EXIT_SUCCESS : EXIT_FAILURE;

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cerrno>
+#include <chrono>
 #include <cstdarg>
 #include <thread>
 #include <cstdio>
@@ -21,6 +22,8 @@
 
 #include "dash.h"
 #include "dash_device.h"
+#include "dash_ingest.h"
+#include "dash_text.h"
 
 struct dash_ctx {
     dash_cfg cfg{};
@@ -59,6 +62,21 @@ struct dash_ctx {
     bool loaded = false;
     bool ran = false;
     char msg[256] = {0};
+    // device-side text ingest (dash_load_text / dash_load_dirs_device): buffers grown on first
+    // use and kept, so a repeated load allocates nothing
+    uint8_t* d_text = nullptr;  // text slab
+    uint64_t d_text_cap = 0;
+    uint64_t* d_foff = nullptr;  // per file of a launch: offset, length
+    uint32_t* d_flen = nullptr;
+    uint64_t d_files_cap = 0;
+    unsigned long long* d_fail = nullptr;  // first-failure cell (dash_ingest.h)
+    char* pin[2] = {nullptr, nullptr};     // pinned slabs of dash_load_dirs_device
+    uint64_t pin_cap = 0;
+    uint64_t* pin_off[2] = {nullptr, nullptr};
+    uint32_t* pin_len[2] = {nullptr, nullptr};
+    uint64_t pin_files_cap = 0;
+    hipEvent_t iev[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+    dash_ingest_report ingest{};
 };
 
 static int fail(dash_t* h, int code, const char* fmt, ...) {
@@ -145,6 +163,17 @@ static void release(dash_t* h) {
     (void)hipFree(h->d_hint);
     (void)hipFree(h->d_skip);
     (void)hipFree(h->d_arb);
+    (void)hipFree(h->d_text);
+    (void)hipFree(h->d_foff);
+    (void)hipFree(h->d_flen);
+    (void)hipFree(h->d_fail);
+    for (int i = 0; i < 2; i++) {
+        if (h->pin[i]) (void)hipHostFree(h->pin[i]);
+        if (h->pin_off[i]) (void)hipHostFree(h->pin_off[i]);
+        if (h->pin_len[i]) (void)hipHostFree(h->pin_len[i]);
+        for (int k = 0; k < 3; k++)
+            if (h->iev[i][k]) (void)hipEventDestroy(h->iev[i][k]);
+    }
     if (h->side) (void)hipStreamSynchronize(h->side);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
@@ -729,6 +758,315 @@ int dash_load_dirs(dash_t* h, const char* const* dirs, uint64_t n) {
         if (bad.load() != ~0ull)
             return fail(h, bad_rc.load(), "%s: trace directory rejected (%d)", dirs[bad.load()], bad_rc.load());
         return dash_load_traces(h, tr.data(), stride, lens.data(), n);
+    });
+}
+
+// ---- device-side text ingest (dash_ingest.hip) ----
+
+// device buffers for a launch over `files` files and `bytes` of text; the events and the cell
+static int ingest_reserve(dash_t* h, uint64_t bytes, uint64_t files) {
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (!h->d_fail) HIPCHK(h, hipMalloc(&h->d_fail, sizeof(unsigned long long)));
+    for (int i = 0; i < 2; i++)
+        for (int k = 0; k < 3; k++)
+            if (!h->iev[i][k]) HIPCHK(h, hipEventCreate(&h->iev[i][k]));
+    if (bytes > h->d_text_cap || !h->d_text) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        (void)hipFree(h->d_text);
+        h->d_text = nullptr;
+        h->d_text_cap = 0;
+        if (hipMalloc(&h->d_text, std::max<uint64_t>(bytes, 16)) != hipSuccess)
+            return fail(h, DASH_ENOMEM, "text slab of %llu bytes: out of device memory", (unsigned long long)bytes);
+        h->d_text_cap = std::max<uint64_t>(bytes, 16);
+    }
+    if (files > h->d_files_cap || !h->d_foff) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        (void)hipFree(h->d_foff);
+        (void)hipFree(h->d_flen);
+        h->d_foff = nullptr;
+        h->d_flen = nullptr;
+        h->d_files_cap = 0;
+        const uint64_t cap = std::max<uint64_t>(files, 1);
+        if (hipMalloc(&h->d_foff, cap * sizeof(uint64_t)) != hipSuccess ||
+            hipMalloc(&h->d_flen, cap * sizeof(uint32_t)) != hipSuccess)
+            return fail(h, DASH_ENOMEM, "file table of %llu entries: out of device memory", (unsigned long long)cap);
+        h->d_files_cap = cap;
+    }
+    return DASH_OK;
+}
+
+static dash::IngestArgs ingest_args(dash_t* h, uint64_t file_base, uint64_t files) {
+    dash::IngestArgs a{};
+    a.text = h->d_text;
+    a.offsets = h->d_foff;
+    a.lengths = h->d_flen;
+    a.file_base = file_base;
+    a.num_files = files;
+    a.trace = reinterpret_cast<uint16_t*>(h->d_trace);
+    a.lens = h->d_lens;
+    a.nchunks = h->nchunks;  // max_instr <= nchunks * 4 (dash_create)
+    a.seg = h->seg;
+    a.num_procs = h->cfg.num_procs;
+    a.max_instr = h->cfg.max_instr;
+    a.fail = h->d_fail;
+    return a;
+}
+
+// The outcome of an ingest: the kernel's first-failure cell against the reader's first
+// unreadable file (eio_file, ~0 = none); the lowest file index wins. dirs: the directory
+// list (dash_load_dirs_device) or nullptr (dash_load_text).
+static int ingest_finish(dash_t* h, const char* what, unsigned long long cell, uint64_t eio_file,
+                         const char* const* dirs) {
+    const uint32_t N = h->cfg.num_procs;
+    dash_ingest_report& r = h->ingest;
+    r.rc = DASH_OK;
+    r.record = 0;
+    r.file = 0;
+    if (cell != dash::INGEST_NO_FAILURE && (cell >> 28) < eio_file) {
+        r.file = cell >> 28;
+        r.record = (uint32_t)(cell & ((1u << 26) - 1u));
+        r.rc = ((cell >> 26) & 3u) == dash::INGEST_CODE_ADDR ? DASH_EADDR : DASH_EPARSE;
+    } else if (eio_file != ~0ull) {
+        r.file = eio_file;
+        r.rc = DASH_EIO;
+    }
+    if (r.rc == DASH_OK) {
+        h->loaded = true;
+        return DASH_OK;
+    }
+    const unsigned long long sys = r.file / N;
+    const unsigned node = (unsigned)(r.file % N);
+    char where[160];
+    if (dirs) snprintf(where, sizeof where, "%.120s (system %llu)", dirs[sys], sys);
+    else snprintf(where, sizeof where, "system %llu", sys);
+    if (r.rc == DASH_EIO)
+        return fail(h, r.rc, "%s: %s: node %u: core_%u.txt missing or unreadable (%d)", what, where, node, node, r.rc);
+    return fail(h, r.rc, "%s: %s: node %u: record %u %s (%d)", what, where, node, r.record,
+                r.rc == DASH_EADDR ? "names an address homed on a node >= num_procs" : "is no RD / WR record", r.rc);
+}
+
+int dash_load_text(dash_t* h, const char* text, const uint64_t* offsets, const uint32_t* lengths,
+                   uint64_t num_files) {
+    return guarded(h, "dash_load_text", [&]() -> int {
+        if (!h || ((!offsets || !lengths) && num_files)) return DASH_EINVAL;
+        if (num_files != h->cfg.num_systems * h->cfg.num_procs)
+            return fail(h, DASH_EINVAL, "dash_load_text: %llu files for %llu systems of %u nodes",
+                        (unsigned long long)num_files, (unsigned long long)h->cfg.num_systems, h->cfg.num_procs);
+        uint64_t bytes = 0;
+        for (uint64_t f = 0; f < num_files; f++) {
+            if (offsets[f] + lengths[f] < offsets[f]) return fail(h, DASH_EINVAL, "dash_load_text: file %llu wraps", (unsigned long long)f);
+            bytes = std::max<uint64_t>(bytes, offsets[f] + lengths[f]);
+        }
+        if (!text && bytes) return DASH_EINVAL;
+        h->ingest = dash_ingest_report{};
+        // the parser writes the trace buffer in place: whatever was loaded is gone from here on
+        h->loaded = false;
+        h->ran = false;
+        int rc = ingest_reserve(h, bytes, num_files);
+        if (rc != DASH_OK) return rc;
+        unsigned long long cell = dash::INGEST_NO_FAILURE;
+        HIPCHK(h, hipMemsetAsync(h->d_fail, 0xFF, sizeof cell, h->stream));
+        HIPCHK(h, hipEventRecord(h->iev[0][0], h->stream));
+        if (bytes) HIPCHK(h, hipMemcpyAsync(h->d_text, text, bytes, hipMemcpyHostToDevice, h->stream));
+        if (num_files) {
+            HIPCHK(h, hipMemcpyAsync(h->d_foff, offsets, num_files * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(h->d_flen, lengths, num_files * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        }
+        HIPCHK(h, hipEventRecord(h->iev[0][1], h->stream));
+        HIPCHK(h, dash::launch_ingest(ingest_args(h, 0, num_files), h->stream));
+        HIPCHK(h, hipEventRecord(h->iev[0][2], h->stream));
+        HIPCHK(h, reset_hint(h));
+        HIPCHK(h, hipMemcpyAsync(&cell, h->d_fail, sizeof cell, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        float c = 0.f, p = 0.f;
+        HIPCHK(h, hipEventElapsedTime(&c, h->iev[0][0], h->iev[0][1]));
+        HIPCHK(h, hipEventElapsedTime(&p, h->iev[0][1], h->iev[0][2]));
+        h->ingest.text_bytes = bytes;
+        h->ingest.copy_ms = c;
+        h->ingest.parse_ms = p;
+        return ingest_finish(h, "dash_load_text", cell, ~0ull, nullptr);
+    });
+}
+
+int dash_load_dirs_device(dash_t* h, const char* const* dirs, uint64_t n) {
+    return guarded(h, "dash_load_dirs_device", [&]() -> int {
+        if (!h || (!dirs && n)) return DASH_EINVAL;
+        if (n != h->cfg.num_systems) return fail(h, DASH_EINVAL, "%llu directories for %llu systems",
+                                                 (unsigned long long)n, (unsigned long long)h->cfg.num_systems);
+        const uint32_t N = h->cfg.num_procs;
+        const uint64_t limit = dash_text_limit(h->cfg.max_instr);  // a file's share, < 2^32
+        const uint64_t slot = std::max<uint64_t>((limit + 15) & ~15ull, 16);  // and its room in a slab
+        // a slab: whole systems, about 64 MiB of room (every file has room for its full share, so
+        // the readers need no sizes in advance; only the bytes read are copied)
+        const uint64_t per_slab = std::max<uint64_t>(1, std::min<uint64_t>(std::max<uint64_t>(n, 1), (64ull << 20) / (slot * N)));
+        const uint64_t slab_files = per_slab * N, slab_cap = slab_files * slot;
+        h->ingest = dash_ingest_report{};
+        h->loaded = false;
+        h->ran = false;
+        int rc = ingest_reserve(h, slab_cap, slab_files);
+        if (rc != DASH_OK) return rc;
+        if (h->pin_cap < slab_cap || h->pin_files_cap < slab_files) {
+            for (int i = 0; i < 2; i++) {
+                if (h->pin[i]) (void)hipHostFree(h->pin[i]);
+                if (h->pin_off[i]) (void)hipHostFree(h->pin_off[i]);
+                if (h->pin_len[i]) (void)hipHostFree(h->pin_len[i]);
+                h->pin[i] = nullptr;
+                h->pin_off[i] = nullptr;
+                h->pin_len[i] = nullptr;
+            }
+            h->pin_cap = h->pin_files_cap = 0;
+            for (int i = 0; i < 2; i++)
+                if (hipHostMalloc((void**)&h->pin[i], slab_cap, hipHostMallocDefault) != hipSuccess ||
+                    hipHostMalloc((void**)&h->pin_off[i], slab_files * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess ||
+                    hipHostMalloc((void**)&h->pin_len[i], slab_files * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
+                    return fail(h, DASH_ENOMEM, "dash_load_dirs_device: two pinned slabs of %llu bytes: out of memory",
+                                (unsigned long long)slab_cap);
+            h->pin_cap = slab_cap;
+            h->pin_files_cap = slab_files;
+        }
+        const unsigned max_threads = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>({std::max<uint64_t>(n, 1), 16, std::max(1u, std::thread::hardware_concurrency())}));
+        std::atomic<uint64_t> eio{~0ull};  // lowest file the readers could not open
+        unsigned long long cell = dash::INGEST_NO_FAILURE;
+        HIPCHK(h, hipMemsetAsync(h->d_fail, 0xFF, sizeof cell, h->stream));
+        bool pending[2] = {false, false};
+        double read_ms = 0, copy_ms = 0, parse_ms = 0;
+        auto drain = [&](int e) -> int {  // slab e's copy and parse are done: its pinned slab is free
+            if (!pending[e]) return DASH_OK;
+            HIPCHK(h, hipEventSynchronize(h->iev[e][2]));
+            float c = 0.f, p = 0.f;
+            HIPCHK(h, hipEventElapsedTime(&c, h->iev[e][0], h->iev[e][1]));
+            HIPCHK(h, hipEventElapsedTime(&p, h->iev[e][1], h->iev[e][2]));
+            copy_ms += c;
+            parse_ms += p;
+            pending[e] = false;
+            return DASH_OK;
+        };
+        for (uint64_t s0 = 0, i = 0; s0 < n && eio.load() == ~0ull; s0 += per_slab, i++) {
+            const int e = (int)(i & 1);
+            if ((rc = drain(e)) != DASH_OK) return rc;
+            const uint64_t cnt = std::min(per_slab, n - s0);
+            const unsigned nt = (unsigned)std::min<uint64_t>(max_threads, cnt);
+            char* slab = h->pin[e];
+            uint64_t* off = h->pin_off[e];
+            uint32_t* len = h->pin_len[e];
+            std::vector<uint64_t> used(nt, 0);
+            // reader j: systems [s0 + cnt * j / nt, s0 + cnt * (j + 1) / nt), back to back from
+            // its region's start, each file on a 16-byte boundary (dash_read_dirs_text's layout)
+            auto reader = [&](unsigned j) {
+                const uint64_t a = cnt * j / nt, b = cnt * (j + 1) / nt;
+                const uint64_t region = a * N * slot;
+                for (uint64_t f = a * N; f < b * N; f++) {
+                    off[f] = region;
+                    len[f] = 0;  // a file not reached parses as empty
+                }
+                uint64_t pos = region, end = region;
+                char base[4096], path[4200];
+                int r = DASH_OK;
+                for (uint64_t k = a; k < b && r == DASH_OK; k++) {
+                    uint32_t t = 0;  // an unresolved directory fails at its node 0
+                    r = dash_resolve_dir(dirs[s0 + k], base, sizeof base);
+                    for (; r == DASH_OK && t < N; t++) {
+                        pos = (end + 15) & ~15ull;
+                        uint64_t got = 0;
+                        snprintf(path, sizeof path, "%s/core_%u.txt", base, t);
+                        // room: the region holds a full share for every file of its systems
+                        if ((r = dashi_read_text_file(path, limit, slab + pos, limit, &got)) != DASH_OK) break;
+                        off[k * N + t] = pos;
+                        len[k * N + t] = (uint32_t)got;
+                        end = pos + got;
+                    }
+                    if (r != DASH_OK) {
+                        const uint64_t f = (s0 + k) * N + t;
+                        uint64_t prev = eio.load();
+                        while (f < prev && !eio.compare_exchange_weak(prev, f)) {
+                        }
+                    }
+                }
+                used[j] = end - region;
+            };
+            const auto t0 = std::chrono::steady_clock::now();
+            {
+                std::vector<std::thread> pool;
+                unsigned started = 1;
+                try {
+                    for (; started < nt; started++) pool.emplace_back(reader, started);
+                } catch (...) {  // no thread: the calling thread reads the remaining regions
+                }
+                reader(0);
+                for (unsigned j = started; j < nt; j++) reader(j);
+                for (auto& th : pool) th.join();
+            }
+            read_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            HIPCHK(h, hipEventRecord(h->iev[e][0], h->stream));
+            for (unsigned j = 0; j < nt; j++) {
+                const uint64_t region = (cnt * j / nt) * N * slot;
+                if (used[j])
+                    HIPCHK(h, hipMemcpyAsync(h->d_text + region, slab + region, used[j], hipMemcpyHostToDevice, h->stream));
+                h->ingest.text_bytes += used[j];
+            }
+            HIPCHK(h, hipMemcpyAsync(h->d_foff, off, cnt * N * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(h->d_flen, len, cnt * N * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipEventRecord(h->iev[e][1], h->stream));
+            HIPCHK(h, dash::launch_ingest(ingest_args(h, s0 * N, cnt * N), h->stream));
+            HIPCHK(h, hipEventRecord(h->iev[e][2], h->stream));
+            pending[e] = true;
+        }
+        HIPCHK(h, reset_hint(h));
+        HIPCHK(h, hipMemcpyAsync(&cell, h->d_fail, sizeof cell, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if ((rc = drain(0)) != DASH_OK || (rc = drain(1)) != DASH_OK) return rc;
+        h->ingest.read_ms = read_ms;
+        h->ingest.copy_ms = copy_ms;
+        h->ingest.parse_ms = parse_ms;
+        return ingest_finish(h, "dash_load_dirs_device", cell, eio.load(), dirs);
+    });
+}
+
+int dash_ingest_info(const dash_t* h, dash_ingest_report* out) {
+    if (!h || !out) return DASH_EINVAL;
+    *out = h->ingest;
+    return DASH_OK;
+}
+
+int dash_read_traces(dash_t* h, uint16_t* packed, uint64_t stride, uint32_t* lens) {
+    return guarded(h, "dash_read_traces", [&]() -> int {
+        if (!h || !lens) return DASH_EINVAL;
+        if (!h->loaded) return fail(h, DASH_ESTATE, "no traces loaded");
+        const uint32_t N = h->cfg.num_procs, P = h->seg;
+        const uint64_t rows = h->cfg.num_systems * N;
+        if (!packed && rows && stride) return DASH_EINVAL;
+        HIPCHK(h, hipSetDevice(h->cfg.device));
+        if (rows) HIPCHK(h, hipMemcpyAsync(lens, h->d_lens, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (uint64_t r = 0; r < rows; r++)
+            if (lens[r] > stride)
+                return fail(h, DASH_EINVAL, "dash_read_traces: trace %llu holds %u words, stride %llu",
+                            (unsigned long long)r, lens[r], (unsigned long long)stride);
+        constexpr uint32_t C = dash::CHUNK_INSTR;
+        const uint64_t pitch = (uint64_t)h->nchunks * 8;  // device row stride in bytes
+        const uint64_t width = std::min<uint64_t>(stride * 2, pitch);
+        if (rows && width) {
+            if (P == N) {  // system s node t is row s * N + t in both layouts
+                HIPCHK(h, hipMemcpy2DAsync(packed, stride * 2, h->d_trace, pitch, width, rows, hipMemcpyDeviceToHost,
+                                           h->stream));
+                HIPCHK(h, hipStreamSynchronize(h->stream));
+            } else {
+                const uint64_t words = h->groups * (uint64_t)h->nchunks * 64;
+                std::vector<uint16_t> host(words * C);
+                HIPCHK(h, hipMemcpyAsync(host.data(), h->d_trace, words * 8, hipMemcpyDeviceToHost, h->stream));
+                HIPCHK(h, hipStreamSynchronize(h->stream));
+                for (uint64_t s = 0; s < h->cfg.num_systems; s++) {
+                    const uint64_t g = s / (64 / P);
+                    const uint32_t lane0 = (uint32_t)(s % (64 / P)) * P;
+                    for (uint32_t t = 0; t < N; t++)
+                        memcpy(packed + (s * N + t) * stride, &host[(g * 64 + lane0 + t) * h->nchunks * C],
+                               (size_t)lens[s * N + t] * 2);
+                }
+            }
+        }
+        for (uint64_t r = 0; r < rows; r++)  // words at or past a row's length have no defined content
+            if (stride > lens[r]) memset(packed + r * stride + lens[r], 0, (size_t)(stride - lens[r]) * 2);
+        return DASH_OK;
     });
 }
 

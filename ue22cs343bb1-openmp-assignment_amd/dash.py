@@ -7,7 +7,10 @@ The reference (assignment.c) exposes: the CLI `./cache_simulator <dir>`
 libdash:
 
     parse_core_file(path)          -> initializeProcessor's parse (:822-850)
+    parse_core_text(bytes)         -> the same parse on bytes in memory
     Engine(...).load_dir(dir)      -> initializeProcessor per node (:152)
+    Engine.load_text(blobs)        -> the same parse on the GPU, many systems per call
+    Engine.load_dirs(dirs, device) -> bulk directory ingest, parsed on the host or the GPU
     Engine.run()                   -> the OpenMP parallel region (:149-738)
     Engine.read_state(sys)         -> the nodes' processorNode state
     dump_node(state, node)         -> printProcessorState bytes (:868-902)
@@ -54,7 +57,9 @@ EXPORTS = ("dash_create", "dash_destroy", "dash_last_error", "dash_load_traces",
            "dash_dump_node", "dash_dump_file", "dash_digest_node", "dash_simulate_dir",
            "dash_read_events", "dash_format_event", "dash_load_dirs", "dash_dump_system",
            "dash_write_digests", "dash_run_host_batched", "dash_set_schedule", "dash_probe_box",
-           "dash_set_micro_schedule")
+           "dash_set_micro_schedule", "dash_parse_core_text", "dash_read_dirs_text", "dash_load_text",
+           "dash_load_dirs_device", "dash_read_traces", "dash_ingest_info")
+TEXT_TILE = 4096  # DASH_TEXT_TILE: bytes per tile of the device text parser
 SIT_OUT = 0xFF
 MICRO_STEP, MICRO_SEND = 0, 1  # dash_set_micro_schedule actions
 
@@ -112,6 +117,12 @@ class BoxProbe(ctypes.Structure):
                 ("probe_sclk_max_mhz", ctypes.c_double)]
 
 
+class IngestReport(ctypes.Structure):
+    _fields_ = [("rc", ctypes.c_int32), ("record", ctypes.c_uint32), ("file", ctypes.c_uint64),
+                ("text_bytes", ctypes.c_uint64), ("read_ms", ctypes.c_double), ("copy_ms", ctypes.c_double),
+                ("parse_ms", ctypes.c_double)]
+
+
 class Gen(ctypes.Structure):
     _fields_ = [("seed", ctypes.c_uint64), ("sys_base", ctypes.c_uint64), ("kind", ctypes.c_uint32),
                 ("locality", ctypes.c_uint32), ("len", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
@@ -163,6 +174,13 @@ def lib() -> ctypes.CDLL:
         "dash_format_event": (i32, [ctypes.POINTER(Event), ctypes.c_char_p, ctypes.c_size_t]),
         "dash_run_host_batched": (i32, [ctypes.POINTER(Cfg), vp, u64, vp, u64, u32, ctypes.POINTER(Stats),
                                         vp, vp, vp]),
+        "dash_parse_core_text": (i32, [ctypes.c_char_p, ctypes.c_size_t, u32, u32, vp, ctypes.POINTER(u32)]),
+        "dash_read_dirs_text": (i32, [ctypes.POINTER(ctypes.c_char_p), u64, u32, u32, vp, u64, vp, vp,
+                                      ctypes.POINTER(u64)]),
+        "dash_load_text": (i32, [vp, vp, vp, vp, u64]),
+        "dash_load_dirs_device": (i32, [vp, ctypes.POINTER(ctypes.c_char_p), u64]),
+        "dash_read_traces": (i32, [vp, vp, u64, vp]),
+        "dash_ingest_info": (i32, [vp, ctypes.POINTER(IngestReport)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -195,6 +213,51 @@ def parse_core_file(path, num_procs=4, max_instr=32) -> np.ndarray:
     _check(lib().dash_parse_core_file(str(path).encode(), num_procs, max_instr,
                                       out.ctypes.data, ctypes.byref(n)), f"parse {path}")
     return out[:n.value].copy()
+
+
+def parse_core_text(data: bytes, num_procs=4, max_instr=32):
+    """dash_parse_core_text: dash_parse_core_file's rules on bytes in memory. Returns (accepted
+    words, rc) and does not raise on DASH_EPARSE / DASH_EADDR: the words are those accepted
+    before the failing record."""
+    data = bytes(data)
+    out = np.zeros(max(max_instr, 1), dtype=np.uint16)
+    n = ctypes.c_uint32(0)
+    rc = lib().dash_parse_core_text(data, len(data), num_procs, max_instr, out.ctypes.data, ctypes.byref(n))
+    return out[:n.value].copy(), rc
+
+
+def pack_text(blobs):
+    """One slab for dash_load_text: the blobs back to back, each on a 16-byte boundary.
+    Returns (slab bytes, offsets u64, lengths u32)."""
+    lengths = np.array([len(b) for b in blobs], dtype=np.uint32)
+    padded = (lengths.astype(np.uint64) + np.uint64(15)) & ~np.uint64(15)
+    offsets = np.zeros(len(blobs), dtype=np.uint64)
+    if len(blobs):
+        offsets[1:] = np.cumsum(padded)[:-1]
+    slab = bytearray(int(padded.sum()))
+    for b, o in zip(blobs, offsets):
+        slab[int(o):int(o) + len(b)] = b
+    return bytes(slab), offsets, lengths
+
+
+def read_dirs_text(dirs, num_procs=4, max_instr=32, cap=None):
+    """dash_read_dirs_text: (rc, need, slab bytes, offsets, lengths). cap=None measures first and
+    reads into a buffer of exactly `need` bytes; cap=k reads into a buffer of k bytes."""
+    arr = (ctypes.c_char_p * max(len(dirs), 1))(*[str(d).encode() for d in dirs])
+    nf = len(dirs) * num_procs
+    off = np.zeros(max(nf, 1), dtype=np.uint64)
+    ln = np.zeros(max(nf, 1), dtype=np.uint32)
+    need = ctypes.c_uint64(0)
+    if cap is None:
+        rc = lib().dash_read_dirs_text(arr, len(dirs), num_procs, max_instr, None, 0, off.ctypes.data,
+                                       ln.ctypes.data, ctypes.byref(need))
+        if rc != OK:
+            return rc, need.value, b"", off[:nf], ln[:nf]
+        cap = need.value
+    buf = ctypes.create_string_buffer(max(cap, 1))
+    rc = lib().dash_read_dirs_text(arr, len(dirs), num_procs, max_instr, buf, cap, off.ctypes.data,
+                                   ln.ctypes.data, ctypes.byref(need))
+    return rc, need.value, buf.raw[:cap], off[:nf], ln[:nf]
 
 
 def init_node_state(node_id: int, cache_size=4) -> NodeState:
@@ -310,10 +373,51 @@ class Engine:
     def load_dir(self, test_dir):
         _check(lib().dash_load_dir(self.h, str(test_dir).encode(), 0), "dash_load_dir", self.h)
 
-    def load_dirs(self, dirs):
-        """Bulk ingest: system k = trace directory dirs[k]."""
+    def load_dirs(self, dirs, device=False):
+        """Bulk ingest: system k = trace directory dirs[k]. device=True parses the text on the
+        GPU (dash_load_dirs_device); after a failure of that path the handle is not loaded."""
         arr = (ctypes.c_char_p * max(len(dirs), 1))(*[str(d).encode() for d in dirs])
-        _check(lib().dash_load_dirs(self.h, arr, len(dirs)), "dash_load_dirs", self.h)
+        if device:
+            _check(lib().dash_load_dirs_device(self.h, arr, len(dirs)), "dash_load_dirs_device", self.h)
+        else:
+            _check(lib().dash_load_dirs(self.h, arr, len(dirs)), "dash_load_dirs", self.h)
+
+    def load_text(self, blobs):
+        """dash_load_text: blobs[system][node] = the bytes of that node's core_<n>.txt, parsed on
+        the GPU straight into the simulator's layout."""
+        flat = [bytes(b) for row in blobs for b in row]
+        assert len(blobs) == self.num_systems and len(flat) == self.num_systems * self.num_procs
+        self.load_text_slab(*pack_text(flat))
+
+    def load_text_slab(self, slab: bytes, offsets, lengths):
+        """dash_load_text on a caller-laid-out slab: file sys * num_procs + node is
+        slab[offsets[f] : offsets[f] + lengths[f]] (any alignment)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+        assert offsets.shape == lengths.shape == (self.num_systems * self.num_procs,)
+        assert not len(offsets) or int((offsets + lengths.astype(np.uint64)).max()) <= len(slab)
+        slab = bytes(slab)  # read in place by the call (no copy for a bytes object)
+        ptr = ctypes.cast(ctypes.c_char_p(slab), ctypes.c_void_p)
+        _check(lib().dash_load_text(self.h, ptr, offsets.ctypes.data, lengths.ctypes.data, len(offsets)),
+               "dash_load_text", self.h)
+
+    def read_traces(self):
+        """dash_read_traces: (packed [systems, num_procs, max_instr] u16, lens [systems, num_procs])
+        as the device holds them; words at or past a node's length read as 0."""
+        stride = max(int(self.cfg.max_instr), 1)
+        packed = np.zeros((self.num_systems, self.num_procs, stride), dtype=np.uint16)
+        lens = np.zeros((self.num_systems, self.num_procs), dtype=np.uint32)
+        _check(lib().dash_read_traces(self.h, packed.ctypes.data, stride, lens.ctypes.data), "dash_read_traces",
+               self.h)
+        return packed, lens
+
+    def ingest_info(self) -> dict:
+        """dash_ingest_info: the last load_text / load_dirs(device=True) as numbers."""
+        r = IngestReport()
+        _check(lib().dash_ingest_info(self.h, ctypes.byref(r)), "dash_ingest_info", self.h)
+        d = {f: getattr(r, f) for f, _ in IngestReport._fields_}
+        d["system"], d["node"] = divmod(int(r.file), self.num_procs)
+        return d
 
     def dump_system(self, sys: int, out_dir):
         _check(lib().dash_dump_system(self.h, sys, str(out_dir).encode()), "dash_dump_system", self.h)
