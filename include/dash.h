@@ -210,6 +210,34 @@ int dash_set_schedule(dash_t *h, const uint8_t *sched, uint32_t rounds);
 #define DASH_MICRO_STEP 0u
 #define DASH_MICRO_SEND 1u
 int dash_set_micro_schedule(dash_t *h, const uint8_t *acts, uint32_t rounds);
+/* A schedule seed per system (same handle requirement as dash_set_schedule: created with
+   schedule_seed != 0, DASH_ESTATE otherwise, and on a handle that follows a micro-step schedule):
+   system k follows the seeded legal schedule of seeds[k], exactly as a handle created with
+   schedule_seed = seeds[k] would run it, whichever queue-depth tiers it passes through; a system
+   whose seed is 0 runs the lockstep schedule, so a batch can carry its own lockstep baseline.
+   n == cfg.num_systems (DASH_EINVAL otherwise); the seeds are on the device before return. No
+   round table is built: each wave hashes its systems' round words as it goes. seeds == NULL with
+   n == 0 returns the handle to its own seed and table. dash_set_system_seeds and
+   dash_set_schedule replace each other: the last call wins. */
+int dash_set_system_seeds(dash_t *h, const uint64_t *seeds, uint64_t n);
+/* After any successful load: every system becomes a copy of system src (trace rows and lengths,
+   copied on the device). The handle stays loaded. */
+int dash_broadcast_system(dash_t *h, uint64_t src);
+/* Which final states can one system's traces reach, how often, and under which schedule?
+   Broadcasts system src, then runs num_seeds schedules, seeds first_seed + i, in passes of
+   cfg.num_systems systems (dash_set_system_seeds; the last pass pads with repeats that are not
+   counted). The distinct (digest, errors) outcomes come back ordered by their witness, the lowest
+   seed that reached them: up to cap into out, their total into *n, which may exceed cap (cap 0
+   with out NULL: count only). Seed 0 is the lockstep schedule. Handle requirements as
+   dash_set_system_seeds, and loaded. Afterwards the handle holds the last pass: its seeds stay
+   set, and with DASH_KEEP_STATE its states are readable (dash_read_state, dash_dump_system).
+   dash_seed_schedule turns a witness seed into a schedule for dash_set_schedule. */
+typedef struct dash_outcome {
+    uint64_t digest, count, seed; /* seed: the lowest one that reached it */
+    uint32_t rounds, errors;      /* of that witness */
+} dash_outcome;
+int dash_explore(dash_t *h, uint64_t src, uint64_t first_seed, uint64_t num_seeds,
+                 dash_outcome *out, uint32_t cap, uint32_t *n);
 int dash_run(dash_t *h, dash_stats *stats);
 int dash_read_state(dash_t *h, uint64_t sys, dash_node_state *out /* [num_procs] */);
 int dash_read_results(dash_t *h, uint64_t first, uint64_t count, uint64_t *digests,
@@ -245,6 +273,13 @@ typedef struct dash_box_probe {
 int dash_probe_box(int device, dash_box_probe *out);
 
 /* ---- host boundary (pure C, no device) ---- */
+/* The seeded schedule of `seed` as a dash_set_schedule table: sched[r * num_procs + t] =
+   DASH_SIT_OUT or node t's delivery position in round r, for rounds [0, rounds) -- what a handle
+   created with schedule_seed = seed, or a system given that seed by dash_set_system_seeds, follows
+   in those rounds (seed 0: the lockstep rounds, every node at position t). A table of at least
+   the run's rounds reproduces the run; it can be read, edited and kept (tests/golden/schedules/).
+   DASH_EINVAL for num_procs outside 1..8 or sched == NULL. */
+int dash_seed_schedule(uint64_t seed, uint32_t num_procs, uint32_t rounds, uint8_t *sched);
 /* initializeProcessor's parse (ref :822-850): up to max_instr records into out[]. */
 int dash_parse_core_file(const char *path, uint32_t num_procs, uint32_t max_instr,
                          uint16_t *out, uint32_t *len);

@@ -174,6 +174,30 @@ static void random_systems(void) {
     CHECK(instr == 16 * 8 * 64, "batch instructions %llu", (unsigned long long)instr);
 }
 
+/* dash_seed_schedule into heap tables of exactly rounds x num_procs bytes (an overrun is an ASan
+   report), every entry against the oracle's twins */
+static void seed_schedules(void) {
+    for (int it = 0; it < 200; it++) {
+        const uint32_t N = 1 + rndn(8), R = rndn(200);
+        const uint64_t seed = it == 0 ? ~0ull : it == 1 ? 1ull << 63 : (rnd() | 1);
+        uint32_t P = 1;
+        while (P < N) P <<= 1;
+        uint8_t *tab = (uint8_t *)malloc((size_t)R * N + (R ? 0 : 1));
+        CHECK(dash_seed_schedule(seed, N, R, tab) == DASH_OK, "seed_schedule it %d", it);
+        for (uint32_t r = 0; r < R; r++)
+            for (uint32_t t = 0; t < N; t++)
+                CHECK(tab[r * N + t] == (orc_arb_stall(seed, r, t) ? DASH_SIT_OUT : orc_arb_prio(seed, r, t, P)),
+                      "seed_schedule it %d round %u node %u", it, r, t);
+        CHECK(dash_seed_schedule(0, N, R, tab) == DASH_OK, "lockstep table it %d", it);
+        for (uint32_t r = 0; r < R; r++)
+            for (uint32_t t = 0; t < N; t++) CHECK(tab[r * N + t] == t, "lockstep table it %d", it);
+        free(tab);
+    }
+    uint8_t one[8];
+    CHECK(dash_seed_schedule(1, 0, 1, one) == DASH_EINVAL && dash_seed_schedule(1, 9, 1, one) == DASH_EINVAL &&
+              dash_seed_schedule(1, 4, 1, NULL) == DASH_EINVAL, "seed_schedule argument checks");
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s SCRATCH_DIR GOLDEN_DIR...\n", argv[0]);
@@ -182,6 +206,7 @@ int main(int argc, char **argv) {
     for (int i = 2; i < argc; i++) golden_dir(argv[i]);
     fuzz_ingest(argv[1]);
     random_systems();
+    seed_schedules();
     if (failures) fprintf(stderr, "%d check(s) failed\n", failures);
     else printf("host sanitizer run clean\n");
     return failures ? 1 : 0;

@@ -23,6 +23,14 @@
  *       tokens, one per round, "P<t>" / "I<t>" / "S<t>" = node t steps (pops or issues, its
  *       sends held), "D<t>" = node t delivers its oldest held message; plain text, or the
  *       "steps" string of a JSON record (tests/golden/ref_runs/micro4.json's cases)
+ *   --write-rounds FILE  after the run, write the schedule it followed (--schedule SEED, or
+ *       lockstep) for the rounds it took as the plain rows --rounds reads, so that
+ *       `--rounds FILE` writes the same dumps and the schedule can be read, edited and kept
+ *   --explore K       which outcomes can this directory reach? Runs K seeded legal schedules,
+ *       seeds S0 .. S0 + K - 1 (S0 = --schedule, default 0 = lockstep first), in one GPU batch
+ *       per 65,536 (dash_explore) and prints one line per distinct final state, "digest(hex)
+ *       count seed rounds errors(hex)", ordered by seed = the lowest seed that reached it
+ *       (`--schedule <seed>` then writes that state's dumps); writes no dumps, exits 0
  *
  * Bulk modes (one GPU batch, many systems; dumps go to OUT_DIR/<k>/):
  *   --batch LIST        system k = the k-th trace directory listed in LIST (one per line)
@@ -189,6 +197,81 @@ static int simulate_traced(const char *dir, unsigned n, unsigned cs, unsigned m,
     return rc;
 }
 
+/* --write-rounds FILE: `rounds` rounds of seed `sched`'s schedule, one row of n characters per round */
+static int write_rounds(const char *path, unsigned long long sched, unsigned n, uint32_t rounds) {
+    uint8_t *tab = (uint8_t *)malloc((size_t)rounds * n + 1);
+    if (!tab) return DASH_ENOMEM;
+    int rc = dash_seed_schedule(sched, n, rounds, tab);
+    FILE *f = rc == DASH_OK ? fopen(path, "w") : NULL;
+    if (rc == DASH_OK && !f) rc = DASH_EIO;
+    for (uint32_t r = 0; f && r < rounds; r++) {
+        char row[DASH_MAX_PROCS + 2];
+        for (unsigned t = 0; t < n; t++) {
+            const uint8_t v = tab[(size_t)r * n + t];
+            row[t] = v == DASH_SIT_OUT ? '-' : (char)('0' + v);
+        }
+        row[n] = '\n';
+        if (fwrite(row, 1, n + 1, f) != n + 1) rc = DASH_EIO;
+    }
+    if (f && fclose(f) != 0) rc = DASH_EIO;
+    free(tab);
+    return rc;
+}
+
+/* --explore K: the distinct outcomes of K seeded schedules of one trace directory */
+static int explore_dir(const char *dir, unsigned n, unsigned cs, unsigned m, int dev, unsigned long long k,
+                       unsigned long long s0) {
+    char base[4096], path[4200];
+    int rc = dash_resolve_dir(dir, base, sizeof base);
+    if (rc != DASH_OK || n < 1 || n > DASH_MAX_PROCS) {
+        fprintf(stderr, "Error: could not open %s/core_0.txt\n", base);
+        return rc != DASH_OK ? rc : DASH_EINVAL;
+    }
+    /* one batch holds up to 65,536 schedules; only system 0's rows are filled on the host (the
+       others are empty until dash_explore copies system 0 over them on the device), and the
+       zeroed buffer stays below 64 MB whatever -m says */
+    const size_t stride = m ? m : 1, row = (size_t)n * stride;
+    uint64_t nsys = k < 65536 ? (k ? k : 1) : 65536;
+    if (nsys > (64u << 20) / (row * 2)) nsys = (64u << 20) / (row * 2) ? (64u << 20) / (row * 2) : 1;
+    uint16_t *tr = (uint16_t *)calloc(nsys * row, sizeof *tr);
+    uint32_t *lens = (uint32_t *)calloc(nsys * n, sizeof *lens);
+    dash_t *h = NULL;
+    dash_cfg cfg = {0};
+    cfg.num_procs = n;
+    cfg.cache_size = cs;
+    cfg.max_instr = m;
+    cfg.num_systems = nsys;
+    cfg.device = dev;
+    cfg.schedule_seed = 1; /* any seeded handle: every system gets a seed of its own */
+    if (!tr || !lens) rc = DASH_ENOMEM;
+    for (unsigned t = 0; rc == DASH_OK && t < n; t++) {
+        snprintf(path, sizeof path, "%s/core_%u.txt", base, t);
+        rc = dash_parse_core_file(path, n, m, tr + t * stride, &lens[t]);
+    }
+    if (rc == DASH_OK && (rc = dash_create(&cfg, &h)) == DASH_OK &&
+        (rc = dash_load_traces(h, tr, stride, lens, nsys)) == DASH_OK) {
+        uint32_t total = 0, cap = 256;
+        dash_outcome *o = (dash_outcome *)malloc(cap * sizeof *o);
+        if (!o) rc = DASH_ENOMEM;
+        else rc = dash_explore(h, 0, s0, k, o, cap, &total);
+        if (rc == DASH_OK && total > cap) { /* rare: once more, with room for all of them */
+            cap = total;
+            free(o);
+            o = (dash_outcome *)malloc((size_t)cap * sizeof *o);
+            rc = o ? dash_explore(h, 0, s0, k, o, cap, &total) : DASH_ENOMEM;
+        }
+        for (uint32_t i = 0; rc == DASH_OK && i < total && i < cap; i++)
+            printf("%016llx %llu %llu %u %x\n", (unsigned long long)o[i].digest, (unsigned long long)o[i].count,
+                   (unsigned long long)o[i].seed, o[i].rounds, o[i].errors);
+        free(o);
+    }
+    if (rc != DASH_OK && h) fprintf(stderr, "%s\n", dash_last_error(h));
+    dash_destroy(h);
+    free(tr);
+    free(lens);
+    return rc;
+}
+
 typedef struct {
     unsigned n, cs, m, len, kind, locality;
     unsigned long long seed, sched;
@@ -293,8 +376,9 @@ int main(int argc, char *argv[]) {
     unsigned n = 4, cs = 4, m = 32;
     int dev = 0, show = 0, dbg_instr = 0, dbg_msg = 0, n_given = 0, device_ingest = 0;
     const char *out = ".", *dir = NULL, *batch = NULL, *digests = NULL, *dump = NULL, *rounds_file = NULL,
-               *micro_file = NULL;
-    unsigned long long synth = 0, seed = 0x5EED, sched = 0;
+               *micro_file = NULL, *write_rounds_file = NULL;
+    unsigned long long synth = 0, seed = 0x5EED, sched = 0, explore = 0;
+    int explore_given = 0;
     unsigned len = 4096, kind = DASH_GEN_UNIFORM;
     double loc = 0.5;
     for (int i = 1; i < argc; i++) {
@@ -316,6 +400,8 @@ int main(int argc, char *argv[]) {
         else if (!strcmp(argv[i], "--schedule") && i + 1 < argc) sched = strtoull(argv[++i], NULL, 0);
         else if (!strcmp(argv[i], "--rounds") && i + 1 < argc) rounds_file = argv[++i];
         else if (!strcmp(argv[i], "--micro") && i + 1 < argc) micro_file = argv[++i];
+        else if (!strcmp(argv[i], "--write-rounds") && i + 1 < argc) write_rounds_file = argv[++i];
+        else if (!strcmp(argv[i], "--explore") && i + 1 < argc) explore = strtoull(argv[++i], NULL, 0), explore_given = 1;
         else if (!strcmp(argv[i], "--locality") && i + 1 < argc) loc = atof(argv[++i]);
         else if (!strcmp(argv[i], "--kind") && i + 1 < argc) {
             const char *k = argv[++i];
@@ -336,6 +422,22 @@ int main(int argc, char *argv[]) {
         fprintf(stderr, "Usage: %s <test_directory>\n", argv[0]); /* ref :128 */
         return EXIT_FAILURE;
     }
+    if (explore_given) {
+        if (rounds_file || micro_file || write_rounds_file) {
+            fprintf(stderr, "cache_simulator: --explore takes no --rounds, --micro or --write-rounds\n");
+            return EXIT_FAILURE;
+        }
+        int rc = explore_dir(dir, n, cs, m, dev, explore, sched);
+        if (rc != DASH_OK) {
+            const char *why = dash_last_error(NULL);
+            fprintf(stderr, "cache_simulator: %s (%d)\n", why[0] ? why : "failed", rc);
+        }
+        return rc == DASH_OK ? EXIT_SUCCESS : EXIT_FAILURE;
+    }
+    if (write_rounds_file && (rounds_file || micro_file)) {  /* the file would restate the seed, not the run */
+        fprintf(stderr, "cache_simulator: --write-rounds goes with --schedule, not with --rounds or --micro\n");
+        return EXIT_FAILURE;
+    }
     uint8_t *rounds = NULL;
     long nrounds = 0;
     if (rounds_file && micro_file) {  /* two schedules for one run: refuse rather than drop one */
@@ -354,11 +456,14 @@ int main(int argc, char *argv[]) {
         return EXIT_FAILURE;
     }
     dash_stats st;
-    int rc = (dbg_instr || dbg_msg || sched || rounds)
+    int rc = (dbg_instr || dbg_msg || sched || rounds || write_rounds_file)
                  ? simulate_traced(dir, n, cs, m, out, dev, dbg_instr, dbg_msg, sched, rounds, nrounds,
                                    micro_file != NULL, &st)
                  : dash_simulate_dir(dir, n, cs, m, out, dev, &st);
     free(rounds);
+    if (rc == DASH_OK && write_rounds_file &&
+        (rc = write_rounds(write_rounds_file, sched, n, (uint32_t)st.rounds_max)) != DASH_OK)
+        fprintf(stderr, "cache_simulator: could not write %s\n", write_rounds_file);
     if (rc != DASH_OK) {
         const char *why = dash_last_error(NULL);
         fprintf(stderr, "cache_simulator: %s (%d)\n", why[0] ? why : "failed", rc);

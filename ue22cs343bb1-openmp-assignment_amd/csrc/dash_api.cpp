@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <new>
 #include <memory>
 #include <vector>
@@ -46,6 +47,9 @@ struct dash_ctx {
     uint32_t* d_arb = nullptr;          // seeded schedule: one word per node and round (dash::arb_node)
     uint32_t arb_len = 0;
     bool micro = false;                 // the round table is a micro-step schedule (MODE 4)
+    uint64_t* d_seeds = nullptr;        // [num_systems] per-system schedule seeds (dash_set_system_seeds)
+    bool per_sys = false;               // the runs follow d_seeds, not the round table
+    bool tab_custom = false;            // the round table holds an explicit schedule, not the handle seed's
     uint32_t* d_event_count = nullptr;  // [sys*N+node]
     uint32_t ev_rounds = 0;             // trace_events rounded up to a multiple of 4
     uint64_t tier_systems[dash::NUM_TIERS] = {};  // systems run per queue-depth tier, last run
@@ -163,6 +167,7 @@ static void release(dash_t* h) {
     (void)hipFree(h->d_hint);
     (void)hipFree(h->d_skip);
     (void)hipFree(h->d_arb);
+    (void)hipFree(h->d_seeds);
     (void)hipFree(h->d_text);
     (void)hipFree(h->d_foff);
     (void)hipFree(h->d_flen);
@@ -413,6 +418,8 @@ int dash_set_schedule(dash_t* h, const uint8_t* sched, uint32_t rounds) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
         h->ran = false;
         h->micro = false;
+        h->per_sys = false;
+        h->tab_custom = true;
         return DASH_OK;
     });
 }
@@ -452,6 +459,100 @@ int dash_set_micro_schedule(dash_t* h, const uint8_t* acts, uint32_t rounds) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
         h->ran = false;
         h->micro = true;
+        h->per_sys = false;
+        h->tab_custom = true;
+        return DASH_OK;
+    });
+}
+
+int dash_set_system_seeds(dash_t* h, const uint64_t* seeds, uint64_t n) {
+    return guarded(h, "dash_set_system_seeds", [&]() -> int {
+        if (!h) return DASH_EINVAL;
+        if (!h->d_arb) return fail(h, DASH_ESTATE, "dash_set_system_seeds: handle created with schedule_seed = 0");
+        if (h->micro) return fail(h, DASH_ESTATE, "dash_set_system_seeds: the handle follows a micro-step schedule");
+        HIPCHK(h, hipSetDevice(h->cfg.device));
+        if (!seeds) {  // back to the handle's own seed and its round table
+            if (n) return fail(h, DASH_EINVAL, "dash_set_system_seeds: null seeds with n = %llu", (unsigned long long)n);
+            if (h->tab_custom) {  // dash_set_schedule overwrote the table
+                HIPCHK(h, dash::launch_arb_table(h->cfg.schedule_seed, h->seg, h->d_arb, h->arb_len, h->stream));
+                h->tab_custom = false;
+            }
+            if (h->per_sys) HIPCHK(h, reset_hint(h));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            h->per_sys = false;
+            h->ran = false;
+            return DASH_OK;
+        }
+        if (n != h->cfg.num_systems)
+            return fail(h, DASH_EINVAL, "dash_set_system_seeds: %llu seeds for %llu systems", (unsigned long long)n,
+                        (unsigned long long)h->cfg.num_systems);
+        if (!h->d_seeds) {
+            hipError_t e = hipMalloc(&h->d_seeds, std::max<uint64_t>(n, 1) * sizeof(uint64_t));
+            if (e != hipSuccess) {
+                h->d_seeds = nullptr;
+                return fail(h, e == hipErrorOutOfMemory ? DASH_ENOMEM : DASH_EDEVICE, "hipMalloc(seeds): %s",
+                            hipGetErrorString(e));
+            }
+        }
+        if (n) HIPCHK(h, hipMemcpyAsync(h->d_seeds, seeds, n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+        // which systems overflow a tier depends on their schedules: the hint of earlier runs is void
+        HIPCHK(h, reset_hint(h));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        h->per_sys = true;
+        h->ran = false;
+        return DASH_OK;
+    });
+}
+
+int dash_broadcast_system(dash_t* h, uint64_t src) {
+    if (!h) return DASH_EINVAL;
+    if (!h->loaded) return fail(h, DASH_ESTATE, "dash_broadcast_system: no traces loaded");
+    if (src >= h->cfg.num_systems) return fail(h, DASH_EINVAL, "dash_broadcast_system: system out of range");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, dash::launch_broadcast(h->d_trace, h->d_lens, h->cfg.num_systems, src, (uint64_t)h->seg * h->nchunks,
+                                     h->cfg.num_procs, h->stream));
+    HIPCHK(h, reset_hint(h));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->ran = false;
+    return DASH_OK;
+}
+
+int dash_explore(dash_t* h, uint64_t src, uint64_t first_seed, uint64_t num_seeds, dash_outcome* out, uint32_t cap,
+                 uint32_t* n) {
+    return guarded(h, "dash_explore", [&]() -> int {
+        if (!h || !n || (!out && cap)) return DASH_EINVAL;
+        *n = 0;
+        const uint64_t nsys = h->cfg.num_systems;
+        if (!h->d_arb) return fail(h, DASH_ESTATE, "dash_explore: handle created with schedule_seed = 0");
+        if (h->micro) return fail(h, DASH_ESTATE, "dash_explore: the handle follows a micro-step schedule");
+        if (num_seeds && !nsys) return fail(h, DASH_EINVAL, "dash_explore: the handle has no systems");
+        int rc = dash_broadcast_system(h, src);
+        if (rc != DASH_OK) return rc;
+        std::vector<uint64_t> seeds(nsys), dig(nsys);
+        std::vector<uint32_t> rnd(nsys), err(nsys);
+        std::vector<dash_outcome> found;
+        std::map<std::pair<uint64_t, uint32_t>, size_t> index;  // (digest, errors) -> found[]
+        for (uint64_t base = 0; base < num_seeds; base += nsys) {
+            const uint64_t fresh = std::min<uint64_t>(nsys, num_seeds - base);
+            // the last pass pads with repeats of its own seeds, which are not counted
+            for (uint64_t i = 0; i < nsys; i++) seeds[i] = first_seed + base + i % fresh;
+            if ((rc = dash_set_system_seeds(h, seeds.data(), nsys)) != DASH_OK) return rc;
+            if ((rc = dash_run(h, nullptr)) != DASH_OK) return rc;
+            if ((rc = dash_read_results(h, 0, nsys, dig.data(), rnd.data(), err.data())) != DASH_OK) return rc;
+            for (uint64_t i = 0; i < fresh; i++) {
+                const auto it = index.emplace(std::make_pair(dig[i], err[i]), found.size());
+                if (it.second) found.push_back(dash_outcome{dig[i], 0, seeds[i], rnd[i], err[i]});
+                dash_outcome& o = found[it.first->second];
+                o.count++;
+                if (seeds[i] < o.seed) {  // only when first_seed + i wrapped past 2^64
+                    o.seed = seeds[i];
+                    o.rounds = rnd[i];
+                }
+            }
+        }
+        std::sort(found.begin(), found.end(), [](const dash_outcome& a, const dash_outcome& b) { return a.seed < b.seed; });
+        *n = (uint32_t)std::min<size_t>(found.size(), 0xFFFFFFFFu);
+        for (size_t k = 0; k < found.size() && k < cap; k++) out[k] = found[k];
         return DASH_OK;
     });
 }
@@ -477,6 +578,10 @@ int dash_run(dash_t* h, dash_stats* stats) {
     a.arb_tab = h->d_arb;
     a.arb_len = h->arb_len;
     a.micro = h->micro ? 1u : 0u;
+    if (h->per_sys) {  // per-system seeds: no table, the seeds ride in the table's pointer (dash_device.h)
+        a.arb_tab = reinterpret_cast<const uint32_t*>(h->d_seeds);
+        a.arb_len = 0;
+    }
     a.cache_size = h->cfg.cache_size;
     for (uint32_t b = 0; b < 16; b++)  // b % CACHE_SIZE for the generic (non-power-of-two) kernels
         a.cs_lut |= (uint64_t)(b % h->cfg.cache_size) << (4 * b);

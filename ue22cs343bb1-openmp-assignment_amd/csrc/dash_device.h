@@ -54,6 +54,9 @@ struct SimArgs {
     uint64_t arb_seed;        // 0: lowest-sender-first lockstep; else the seeded schedule
     const uint32_t* arb_tab;  // seeded schedule: per-round word (arb_word) for rounds < arb_len
     uint32_t arb_len;         // a multiple of 4; rounds beyond it hash their key in the kernel
+                              // (>= 4 for any table). 0: per-system seeds (dash_set_system_seeds),
+                              // arb_tab points at uint64_t seeds[nsys] and arb_seed only selects
+                              // the seeded kernel
     uint32_t micro;           // 1: arb_tab is a micro-step table (dash_set_micro_schedule, MODE 4)
     const uint8_t* skip;      // optional [sys]: 1 = run elsewhere this pass (a deeper tier, concurrently)
     uint32_t cache_size;      // CACHE_SIZE (ref :7); read by the generic (non-power-of-two) kernels
@@ -95,6 +98,9 @@ hipError_t launch_arb_table(uint64_t seed, uint32_t seg, uint32_t* out, uint32_t
 // RD words carry value 0 (ref :839): clears bits 7..0 of every word whose bit 15 is 0
 hipError_t launch_clear_rd(uint2* trace, uint64_t words, hipStream_t s);
 hipError_t launch_mark(const uint32_t* list, uint64_t n, uint8_t* skip, hipStream_t s);
+// every system's trace rows and lengths := system src's (row = seg * nchunks chunks per system)
+hipError_t launch_broadcast(uint2* trace, uint32_t* lens, uint64_t nsys, uint64_t src, uint64_t row, uint32_t N,
+                            hipStream_t s);
 // box probe: blocks x 256 threads, 8 full-rate VALU per trip; clk[2 * block] = shader cycles,
 // clk[2 * block + 1] = 100-MHz reference ticks of that block's loop
 constexpr uint32_t PROBE_VALU_PER_TRIP = 8;

@@ -204,3 +204,24 @@ uint64_t dash_digest_node(const dash_node_state *s, uint32_t node_id, uint32_t c
                         ((uint64_t)s->cache_state[i] << 16) | (1ULL << 24)));
     return h;
 }
+
+/* The seeded schedule's round on the host: the same two hashes as the kernel's
+   arb_word (csrc/dash_kernels.hip), written as a dash_set_schedule table. */
+
+int dash_seed_schedule(uint64_t seed, uint32_t num_procs, uint32_t rounds, uint8_t *sched) {
+    if (num_procs < 1 || num_procs > DASH_MAX_PROCS || !sched) return DASH_EINVAL;
+    uint32_t P = 1;
+    while (P < num_procs) P <<= 1;
+    for (uint64_t r = 0; r < rounds; r++) {
+        const uint64_t rk = seed ^ (r * 0x9E3779B97F4A7C15ULL);
+        const uint64_t key = fmix64(rk), skey = fmix64(rk ^ 0xD1B54A32D192ED03ULL);
+        const uint32_t A = ((uint32_t)key & (P - 1)) | 1u, Bc = (uint32_t)(key >> 8) & (P - 1);
+        for (uint32_t t = 0; t < num_procs; t++) {
+            uint8_t v = (uint8_t)((t * A + Bc) & (P - 1));
+            if (seed == 0) v = (uint8_t)t; /* lockstep: every node steps, ascending sender order */
+            else if (((skey >> (8 * t)) & 3u) == 0) v = DASH_SIT_OUT;
+            sched[r * num_procs + t] = v;
+        }
+    }
+    return DASH_OK;
+}

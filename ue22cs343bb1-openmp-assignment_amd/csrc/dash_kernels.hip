@@ -106,6 +106,17 @@ __device__ __forceinline__ uint32_t arb_word(uint64_t seed, uint32_t round, uint
 __device__ __forceinline__ uint32_t arb_node(uint32_t w, uint32_t t) {
     return ((w >> t) & 1u) ? 0u : 2u << (4u * ((w >> (8 + 3 * t)) & 7u));
 }
+// arb_node(arb_word(seed, round, P), t) for a seed that differs from lane to lane (per-system
+// seeds, dash_set_system_seeds): only node t's own fields of the round word, so the two hashes run
+// once per lane on the vector unit. Seed 0 is the lockstep round: t steps and delivers at position t.
+__device__ __forceinline__ uint32_t arb_lane(uint64_t seed, uint32_t round, uint32_t t, uint32_t P) {
+    const uint64_t rk = seed ^ ((uint64_t)round * 0x9E3779B97F4A7C15ull);
+    const uint64_t key = fmix64(rk), skey = fmix64(rk ^ 0xD1B54A32D192ED03ull);
+    const uint32_t A = ((uint32_t)key & (P - 1)) | 1u, Bc = (uint32_t)(key >> 8) & (P - 1);
+    const bool lock = seed == 0;
+    const uint32_t pos = lock ? t : (t * A + Bc) & (P - 1);
+    return (!lock && ((uint32_t)(skey >> (8 * t)) & 3u) == 0) ? 0u : 2u << (4u * pos);
+}
 
 // CS = CACHE_SIZE; CS = 0 is the generic kernel for a non-power-of-two CACHE_SIZE (read at
 // run time, LDS sized for the maximum of 16 lines)
@@ -172,7 +183,8 @@ __device__ __forceinline__ mask_t Mbit15(uint32_t v) {
 // the fast one anything:
 //   1 = a seeded legal schedule (a.arb_seed != 0, DESIGN.md §2 -- per round, a node sits out
 //       with probability 1/4 and senders deliver in a seeded affine order; oracle twins
-//       orc_arb_stall, orc_arb_prio);
+//       orc_arb_stall, orc_arb_prio); with a.arb_len == 0 every system follows a seed of its own,
+//       hashed per lane at each trip start (dash_set_system_seeds; seed 0 = the lockstep rounds);
 //   2 = the DEBUG_MSG / DEBUG_INSTR event log (a.events) under lockstep;
 //   3 = the event log under a seeded (or explicit) schedule;
 //   4 = an explicit micro-step schedule with the event log (a.micro, dash_set_micro_schedule): per
@@ -364,6 +376,17 @@ void sim_kernel(const SimArgs a) {
     uint4 arbw = make_uint4(0, 0, 0, 0), arbn = make_uint4(0, 0, 0, 0);
     const uint4* const arbt = reinterpret_cast<const uint4*>(a.arb_tab) + t;
     if (ARB && a.arb_len) arbn = arbt[0];
+    // per-system seeds (dash_set_system_seeds): no table -- arb_len == 0, which no table-driven run
+    // has, so every trip hashes its words at the trip start -- and arb_tab holds one 64-bit seed
+    // per system instead, indexed by the system's real id: the same seed on every tier's pass over
+    // it. With no table to prefetch, arbn is idle in this mode and carries the seed in x, y, and
+    // the mode is told by a value the loop tests anyway: the table-driven runs' round loop gains
+    // no register.
+    if (ARB && !MICRO && a.arb_len == 0u) {
+        COLD();
+        const uint64_t sd = live ? reinterpret_cast<const uint64_t*>(a.arb_tab)[sys] : 0ull;
+        arbn = make_uint4((uint32_t)sd, (uint32_t)(sd >> 32), 0u, 0u);
+    }
 
     // Every predicate of a step is a wave-wide lane mask (an SGPR pair): one compare makes
     // it, the scalar unit combines them, v_cndmask consumes them. The kernel is bound by
@@ -794,6 +817,11 @@ void sim_kernel(const SimArgs a) {
                 COLD();
                 if constexpr (MICRO) {  // past a micro-step table every node sits out
                     arbw = make_uint4(0, 0, 0, 0);
+                } else if (a.arb_len == 0u) {  // per-system seeds: a lane value, hashed on the vector unit
+                    COLD();
+                    const uint64_t sd = (uint64_t)arbn.x | ((uint64_t)arbn.y << 32);
+                    arbw = make_uint4(arb_lane(sd, rv, t, P), arb_lane(sd, rv + 1, t, P),
+                                      arb_lane(sd, rv + 2, t, P), arb_lane(sd, rv + 3, t, P));
                 } else {
                     const uint32_t r0 = __builtin_amdgcn_readfirstlane(rv);
                     arbw = make_uint4(arb_node(arb_word(a.arb_seed, r0, P), t),
@@ -1064,6 +1092,33 @@ hipError_t launch_mark(const uint32_t* list, uint64_t n, uint8_t* skip, hipStrea
     if (n == 0) return hipSuccess;
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, 1024);
     hipLaunchKernelGGL(mark_kernel, dim3(blocks), dim3(256), 0, s, list, n, skip);
+    return hipGetLastError();
+}
+
+// every system becomes a copy of system `src` (dash_broadcast_system). The trace layout
+// [group][lane][chunk] is [sys][P lanes][nchunks] in memory (64 = P x systems per wave), so a
+// system is `row` = P * nchunks consecutive chunks; lens hold N words per system.
+__global__ __launch_bounds__(256) void broadcast_kernel(uint2* trace, uint32_t* lens, uint64_t nsys, uint64_t src,
+                                                        uint64_t row, uint32_t N) {
+    const uint64_t total = nsys * row, stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint64_t i = gid; i < total; i += stride) {
+        const uint64_t s = i / row;
+        if (s != src) trace[i] = trace[src * row + (i - s * row)];
+    }
+    for (uint64_t i = gid; i < nsys * N; i += stride) {
+        const uint64_t s = i / N;
+        if (s != src) lens[i] = lens[src * N + (i - s * N)];
+    }
+}
+
+hipError_t launch_broadcast(uint2* trace, uint32_t* lens, uint64_t nsys, uint64_t src, uint64_t row, uint32_t N,
+                            hipStream_t s) {
+    if (nsys == 0 || src >= nsys) return nsys == 0 ? hipSuccess : hipErrorInvalidValue;
+    const uint64_t work = std::max<uint64_t>(nsys * row, nsys * N);
+    const uint64_t blocks = std::min<uint64_t>((work + 255) / 256, 256ull * 64);  // grid-stride
+    hipLaunchKernelGGL(broadcast_kernel, dim3((uint32_t)std::max<uint64_t>(blocks, 1)), dim3(256), 0, s, trace, lens,
+                       nsys, src, row, N);
     return hipGetLastError();
 }
 

@@ -12,6 +12,7 @@ libdash:
     Engine.load_text(blobs)        -> the same parse on the GPU, many systems per call
     Engine.load_dirs(dirs, device) -> bulk directory ingest, parsed on the host or the GPU
     Engine.run()                   -> the OpenMP parallel region (:149-738)
+    Engine.explore(src, s0, k)     -> the outcomes k seeded legal schedules of one system reach
     Engine.read_state(sys)         -> the nodes' processorNode state
     dump_node(state, node)         -> printProcessorState bytes (:868-902)
     simulate_dir(dir, out_dir)     -> main() end to end
@@ -58,7 +59,8 @@ EXPORTS = ("dash_create", "dash_destroy", "dash_last_error", "dash_load_traces",
            "dash_read_events", "dash_format_event", "dash_load_dirs", "dash_dump_system",
            "dash_write_digests", "dash_run_host_batched", "dash_set_schedule", "dash_probe_box",
            "dash_set_micro_schedule", "dash_parse_core_text", "dash_read_dirs_text", "dash_load_text",
-           "dash_load_dirs_device", "dash_read_traces", "dash_ingest_info")
+           "dash_load_dirs_device", "dash_read_traces", "dash_ingest_info", "dash_set_system_seeds",
+           "dash_broadcast_system", "dash_seed_schedule", "dash_explore")
 TEXT_TILE = 4096  # DASH_TEXT_TILE: bytes per tile of the device text parser
 SIT_OUT = 0xFF
 MICRO_STEP, MICRO_SEND = 0, 1  # dash_set_micro_schedule actions
@@ -123,6 +125,11 @@ class IngestReport(ctypes.Structure):
                 ("parse_ms", ctypes.c_double)]
 
 
+class Outcome(ctypes.Structure):
+    _fields_ = [("digest", ctypes.c_uint64), ("count", ctypes.c_uint64), ("seed", ctypes.c_uint64),
+                ("rounds", ctypes.c_uint32), ("errors", ctypes.c_uint32)]
+
+
 class Gen(ctypes.Structure):
     _fields_ = [("seed", ctypes.c_uint64), ("sys_base", ctypes.c_uint64), ("kind", ctypes.c_uint32),
                 ("locality", ctypes.c_uint32), ("len", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
@@ -181,6 +188,10 @@ def lib() -> ctypes.CDLL:
         "dash_load_dirs_device": (i32, [vp, ctypes.POINTER(ctypes.c_char_p), u64]),
         "dash_read_traces": (i32, [vp, vp, u64, vp]),
         "dash_ingest_info": (i32, [vp, ctypes.POINTER(IngestReport)]),
+        "dash_set_system_seeds": (i32, [vp, vp, u64]),
+        "dash_broadcast_system": (i32, [vp, u64]),
+        "dash_seed_schedule": (i32, [u64, u32, u32, vp]),
+        "dash_explore": (i32, [vp, u64, u64, u64, vp, u32, ctypes.POINTER(u32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -289,6 +300,16 @@ def format_events(events, kinds=(0, 1)) -> str:
             _check(n if n < 0 else OK, "dash_format_event")
             out.append(buf.value.decode())
     return "".join(out)
+
+
+def seed_schedule(seed: int, num_procs: int, rounds: int) -> np.ndarray:
+    """dash_seed_schedule: the seeded schedule of `seed` as a set_schedule table, uint8
+    [rounds][num_procs] of SIT_OUT or the node's delivery position (seed 0: lockstep rounds)."""
+    sched = np.zeros((rounds, num_procs), dtype=np.uint8)
+    # a zero-round table still needs a non-null pointer
+    buf = sched if rounds and num_procs else np.zeros(1, dtype=np.uint8)
+    _check(lib().dash_seed_schedule(seed, num_procs, rounds, buf.ctypes.data), "dash_seed_schedule")
+    return sched
 
 
 def probe_box(device=0) -> dict:
@@ -443,6 +464,38 @@ class Engine:
         assert acts.ndim == 2 and acts.shape[1] == self.num_procs
         _check(lib().dash_set_micro_schedule(self.h, acts.ctypes.data, acts.shape[0]), "dash_set_micro_schedule",
                self.h)
+
+    def set_system_seeds(self, seeds):
+        """dash_set_system_seeds: system k follows the seeded schedule of seeds[k] (0 = lockstep);
+        None returns the handle to its own seed. Needs schedule_seed != 0."""
+        if seeds is None:
+            _check(lib().dash_set_system_seeds(self.h, None, 0), "dash_set_system_seeds", self.h)
+            return
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        assert seeds.ndim == 1
+        _check(lib().dash_set_system_seeds(self.h, seeds.ctypes.data, len(seeds)), "dash_set_system_seeds", self.h)
+
+    def broadcast_system(self, src: int):
+        """dash_broadcast_system: every system becomes a copy of system src (on the device)."""
+        _check(lib().dash_broadcast_system(self.h, src), "dash_broadcast_system", self.h)
+
+    def explore(self, src: int, first_seed: int, num_seeds: int, cap=None) -> list:
+        """dash_explore: the distinct outcomes of system src under seeds first_seed + i, i <
+        num_seeds, as dicts (digest, count, seed = the lowest seed that reached it, rounds and errors
+        of that witness), in witness-seed order. cap=k returns the first k; the total is
+        explore_total afterwards either way."""
+        n = ctypes.c_uint32()
+        want = 1024 if cap is None else cap
+        while True:
+            arr = (Outcome * max(want, 1))()
+            _check(lib().dash_explore(self.h, src, first_seed, num_seeds, arr, want, ctypes.byref(n)),
+                   "dash_explore", self.h)
+            if cap is not None or n.value <= want:
+                break
+            want = n.value  # more outcomes than the first guess held: once more, with room for all
+        cap = want
+        self.explore_total = int(n.value)
+        return [{f: int(getattr(o, f)) for f, _ in Outcome._fields_} for o in arr[:min(n.value, cap)]]
 
     def run(self) -> dict:
         st = Stats()
