@@ -15,6 +15,9 @@
  *                          13-way dispatch, sendMessage,
  *                          handleCacheReplacement, locks/queues      :135-155, :149-738,
  *                                                                    :741-765, :767-804
+ *   dash_set_micro_seeds   the threads' interleaving itself: per system,
+ *                          one seeded weighted walk over pops, issues
+ *                          and single sendMessage calls                 :149-738, :741-765
  *   dash_read_state        the private processorNode after the run   :145, :149
  *   dash_dump_node/_file   printProcessorState                       :853-905
  *   dash_simulate_dir      main() end to end                         :126-739
@@ -238,6 +241,54 @@ typedef struct dash_outcome {
 } dash_outcome;
 int dash_explore(dash_t *h, uint64_t src, uint64_t first_seed, uint64_t num_seeds,
                  dash_outcome *out, uint32_t cap, uint32_t *n);
+/* ---- seeded micro-step schedules: one weighted random walk of the reference's own granularity
+   per system ----
+   The schedule (seed, weights) is a micro-step schedule (dash_set_micro_schedule) decided round by
+   round from the system's state. A node is enabled at the start of a round when it holds
+   undelivered sends in its outbox, or its queue can be popped (non-empty and not stuck at 256), or
+   it can issue (not waiting, instructions left). Exactly one enabled node acts in every round in
+   which any node is enabled:
+     - byte t of `weights` is node t's weight w_t, 0..31; W = the sum of w_t over the enabled nodes;
+     - if W == 0 every enabled node counts with weight 1 (so a weight-0 node acts only when no
+       enabled node has positive weight, and the schedule always progresses);
+     - u = the high 32 bits of fmix64(seed ^ round * 0x9E3779B97F4A7C15) (the seeded round
+       schedule's key), x = (u * W) >> 32;
+     - the picked node is the lowest enabled t whose inclusive weight sum over the enabled nodes
+       <= t exceeds x;
+     - it delivers its oldest held send if it holds any (DASH_MICRO_SEND), else it steps
+       (DASH_MICRO_STEP).
+   A node with held sends is never stepped (no DASH_ERR_SCHEDULE), every such run is an execution
+   of the reference at sendMessage granularity, and `rounds` is its number of micro-steps. A send
+   to a node >= num_procs (DASH_ERR_OOB) is held like any other and dropped by its delivery. */
+/* The node that acts in `round` of the seeded micro-step schedule (seed, weights), given the set
+   of enabled nodes; < 0 = DASH_EINVAL (enabled == 0, a bit >= num_procs, a weight byte > 31).
+   Pure host code. */
+int dash_micro_pick(uint64_t seed, uint32_t round, uint32_t enabled, uint64_t weights, uint32_t num_procs);
+#define DASH_MICRO_UNIFORM 0x0101010101010101ull /* every node weight 1 */
+/* System k follows the seeded micro-step schedule (seeds[k], weights[k]); weights == NULL = uniform.
+   Handle requirements as dash_set_system_seeds (schedule_seed != 0, DASH_ESTATE otherwise), but no
+   round table is needed, so any max_rounds goes. n == cfg.num_systems and every weight byte <= 31
+   (DASH_EINVAL otherwise). Runs at queue depth 256 only, as every micro-step schedule.
+   seeds == NULL with n == 0 returns the handle to its own seed and table. It replaces, and is
+   replaced by, dash_set_schedule, dash_set_micro_schedule and dash_set_system_seeds: the last call
+   wins. With an event log (cfg.trace_events) the run records its acts, see dash_read_micro_acts. */
+int dash_set_micro_seeds(dash_t *h, const uint64_t *seeds, const uint64_t *weights, uint64_t n);
+/* The schedule system `sys` followed in the last run under dash_set_micro_seeds, as a
+   dash_set_micro_schedule table acts[r * num_procs + t] for the *rounds rounds it took, rebuilt from
+   the event log (a delivery leaves a marker word there, which dash_read_events never returns).
+   Feeding the table to dash_set_micro_schedule reproduces the run: final state, digest, event log
+   and, for a run that was not cut by the round cap, error bits. One difference: a held send to a
+   node >= num_procs (DASH_ERR_OOB) is dropped by its delivery here but at the step under a table,
+   where that DASH_MICRO_SEND act then finds an empty outbox and does nothing; if it was the
+   system's last act, the replay reports one round fewer. DASH_ESTATE without micro seeds,
+   without a log, or before a run; DASH_ETRUNC when the run is longer than the log; DASH_EINVAL when
+   cap_rounds < *rounds (*rounds is still set, so a call with cap_rounds 0 sizes the table). */
+int dash_read_micro_acts(dash_t *h, uint64_t sys, uint8_t *acts, uint32_t cap_rounds, uint32_t *rounds);
+/* dash_explore over seeded micro-step schedules: seeds first_seed + i with one weight vector for
+   all (dash_set_micro_seeds). Same outcome records, ordering, padding rule and post-state; no seed
+   is special (seed 0 is a schedule like any other). */
+int dash_explore_micro(dash_t *h, uint64_t src, uint64_t first_seed, uint64_t num_seeds, uint64_t weights,
+                       dash_outcome *out, uint32_t cap, uint32_t *n);
 int dash_run(dash_t *h, dash_stats *stats);
 int dash_read_state(dash_t *h, uint64_t sys, dash_node_state *out /* [num_procs] */);
 int dash_read_results(dash_t *h, uint64_t first, uint64_t count, uint64_t *digests,

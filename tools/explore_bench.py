@@ -19,6 +19,12 @@ explore: wall time (host clock around dash_explore, which ends synchronised) of 
 tests/golden/reference/test_4 at 4 nodes, on a 65,536-system handle (16 passes) and on a
 2^20-system handle (one pass); the outcome list must be the same from both.
 Writes profiles/explore.json (--out).
+
+--micro times instead, in one alternating run, dash_explore_micro (seeded micro-step schedules,
+uniform weights) and dash_explore (seeded round schedules) over the same 2^20 seeds of test_4 on
+the same two handles, and the CPU checker's own weighted random walk (orc_random_walk, STRICT
+model) on 16 host threads of the same box; schedules per second by the host clock and the outcome
+counts go to profiles/explore_micro.json (--micro-out).
 """
 import argparse
 import importlib.util
@@ -146,6 +152,78 @@ def explore_wall(dash, args):
     return out
 
 
+def oracle_walk_rate(tr, lens, threads=16, walks=32768):
+    """orc_random_walk (uniform node weights, STRICT) on `threads` host threads: walks per second by
+    the host clock, and the distinct outcomes seen. The library call releases the interpreter lock."""
+    import concurrent.futures
+    import ctypes
+    import oracle_ctypes as oc
+    L = oc.lib()
+    tr, lens = oc._tr(tr, lens)
+
+    def some(k):  # one thread's share, its buffers made once: the loop is the library call
+        cfg = oc.OrcCfg(4, 4, 256, 0, 0, oc.MICRO_STRICT, 0)
+        res, wit, wl = oc.OrcOutcome(), np.zeros(1 << 16, np.uint16), ctypes.c_uint32()
+        digs = []
+        for s in range(k, walks, threads):
+            rc = L.orc_random_walk(ctypes.byref(cfg), tr.ctypes.data, tr.shape[1], lens.ctypes.data, 0, 1 + s, None,
+                                   None, ctypes.addressof(res), wit.ctypes.data, len(wit), ctypes.addressof(wl))
+            assert rc == 0
+            digs.append(int(res.digest))
+        return digs
+    some(walks - 8)  # warm
+    t0 = time.perf_counter()
+    with concurrent.futures.ThreadPoolExecutor(threads) as ex:
+        digs = [d for part in ex.map(some, range(threads)) for d in part]
+    dt = time.perf_counter() - t0
+    return {"threads": threads, "walks": len(digs), "seconds": dt, "walks_per_s": len(digs) / dt,
+            "distinct_outcomes": len(set(digs)), "host_cpus": os.cpu_count()}
+
+
+def explore_micro_wall(dash, args):
+    import oracle_ctypes as oc
+    tr, lens = oc.load_test_dir(oc.GOLDEN / "test_4")
+    total = 1 << 20
+    out = {"what": f"{total} schedules of tests/golden/reference/test_4 (4 nodes), seeds 1 .. 2^20: dash_explore_micro "
+                   "(seeded micro-step schedules, uniform weights) and dash_explore (seeded round schedules) "
+                   "alternating on each handle; host clock around the call, the load of the handle not included",
+           "measured": "seconds, schedules_per_s, the outcome counts, rounds_of_last_pass (dash_stats), "
+                       "oracle_random_walk",
+           "counted_from_the_code": "passes = 2^20 / systems of the handle"}
+    lists = {"micro": [], "rounds": []}
+    for nsys in (1 << 16, 1 << 20):
+        with dash.Engine(nsys, num_procs=4, cache_size=4, max_instr=32, device=args.device, schedule_seed=1) as eng:
+            packed = np.zeros((nsys, 4, tr.shape[1]), np.uint16)
+            ln = np.zeros((nsys, 4), np.uint32)
+            packed[0], ln[0] = tr, lens
+            eng.load_traces(packed, ln)
+            kinds = {"micro": lambda k: eng.explore_micro(0, 1, k), "rounds": lambda k: eng.explore(0, 1, k)}
+            for fn in kinds.values():
+                fn(nsys)  # warm
+            ts = {k: [] for k in kinds}
+            got = {}
+            for _ in range(args.reps):
+                for k, fn in kinds.items():  # alternating
+                    t0 = time.perf_counter()
+                    got[k] = fn(total)
+                    ts[k].append(time.perf_counter() - t0)
+            rec = {"passes": total // nsys}
+            for k in kinds:
+                lists[k].append(got[k])
+                rec[k] = {"seconds": spread(ts[k]), "schedules_per_s": total / statistics.median(ts[k]),
+                          "distinct_outcomes": len(got[k])}
+            eng.set_micro_seeds(np.arange(1, nsys + 1, dtype=np.uint64))
+            st = eng.run()
+            rec["micro_last_pass"] = {"kernel_ms": st["kernel_ms"], "rounds_total": st["rounds_total"],
+                                      "rounds_max": st["rounds_max"], "err_bits": st["err_bits"]}
+        out[f"handle_{nsys}_systems"] = rec
+    for k, v in lists.items():
+        out[f"{k}_outcomes"] = [dict(o, digest=f"{o['digest']:016x}") for o in v[0]]
+        out[f"{k}_same_list_from_both_handles"] = v[0] == v[1]
+    out["oracle_random_walk"] = oracle_walk_rate(tr, lens)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--systems", type=int, default=1 << 20)
@@ -156,6 +234,8 @@ def main():
     ap.add_argument("--parent-pkg", default=None)
     ap.add_argument("--worker", default=None, metavar="PKG", help=argparse.SUPPRESS)
     ap.add_argument("--out", default=str(ROOT / "profiles" / "explore.json"))
+    ap.add_argument("--micro", action="store_true", help="time dash_explore_micro against dash_explore instead")
+    ap.add_argument("--micro-out", default=str(ROOT / "profiles" / "explore_micro.json"))
     args = ap.parse_args()
     if args.worker:  # (b) alone on the package in that directory
         spec = importlib.util.spec_from_file_location("dash_worker", pathlib.Path(args.worker) / "dash.py")
@@ -167,6 +247,13 @@ def main():
     assert args.reps >= 5, "at least five timings of each schedule"
     out = {"tool": "tools/explore_bench.py", "reps": args.reps,
            "box": {k: v for k, v in dash.probe_box(args.device).items() if k in ("name", "arch", "compute_units")}}
+    if args.micro:
+        out["explore_micro"] = explore_micro_wall(dash, args)
+        ok = out["explore_micro"]["micro_same_list_from_both_handles"] and \
+            out["explore_micro"]["rounds_same_list_from_both_handles"]
+        pathlib.Path(args.micro_out).write_text(json.dumps(out, indent=1) + "\n")
+        print(json.dumps({"explore_bench": "ok" if ok else "RESULTS DIFFER", "out": args.micro_out}))
+        return 0 if ok else 1
     out["schedules"] = three_schedules(dash, args)
     print(json.dumps({k: out["schedules"][k] for k in ("b_over_a", "c_over_b")}), flush=True)
     out["explore"] = explore_wall(dash, args)

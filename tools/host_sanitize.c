@@ -198,6 +198,28 @@ static void seed_schedules(void) {
               dash_seed_schedule(1, 4, 1, NULL) == DASH_EINVAL, "seed_schedule argument checks");
 }
 
+/* dash_micro_pick over every enabled set of every node count, weights with zeros and all zero,
+   round numbers around the 32-bit wrap: the pick is an enabled node, of positive weight when any
+   enabled node has one */
+static void micro_picks(void) {
+    for (uint32_t N = 1; N <= 8; N++)
+        for (uint32_t en = 1; en < (1u << N); en++)
+            for (uint32_t k = 0; k < 16; k++) {
+                uint64_t w = rnd() & 0x1F1F1F1F1F1F1F1Full;
+                if (k & 1) w &= rnd() & rnd();
+                if (k == 7) w = 0;
+                uint32_t pos = 0;
+                for (uint32_t t = 0; t < N; t++)
+                    if ((en >> t) & 1u) pos += (uint32_t)(w >> (8 * t)) & 0xFFu;
+                const int t = dash_micro_pick(rnd(), 0xFFFFFFF8u + k, en, w, N);
+                CHECK(t >= 0 && t < (int)N && ((en >> t) & 1u), "micro_pick N %u enabled %x", N, en);
+                CHECK(t < 0 || !pos || ((w >> (8 * t)) & 0xFFu), "micro_pick N %u enabled %x: weight 0 picked", N, en);
+            }
+    CHECK(dash_micro_pick(1, 0, 0, 0, 4) == DASH_EINVAL && dash_micro_pick(1, 0, 16, 0, 4) == DASH_EINVAL &&
+              dash_micro_pick(1, 0, 1, 32, 4) == DASH_EINVAL && dash_micro_pick(1, 0, 1, 0, 9) == DASH_EINVAL,
+          "micro_pick argument checks");
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s SCRATCH_DIR GOLDEN_DIR...\n", argv[0]);
@@ -207,6 +229,7 @@ int main(int argc, char **argv) {
     fuzz_ingest(argv[1]);
     random_systems();
     seed_schedules();
+    micro_picks();
     if (failures) fprintf(stderr, "%d check(s) failed\n", failures);
     else printf("host sanitizer run clean\n");
     return failures ? 1 : 0;

@@ -31,6 +31,15 @@
  *       per 65,536 (dash_explore) and prints one line per distinct final state, "digest(hex)
  *       count seed rounds errors(hex)", ordered by seed = the lowest seed that reached it
  *       (`--schedule <seed>` then writes that state's dumps); writes no dumps, exits 0
+ *   --micro-seed S [--weights a,b,..]  one seeded micro-step schedule (dash_set_micro_seeds): each
+ *       round one enabled node, picked by seed S and the per-node weights (0..31, default all 1;
+ *       a weight-0 node acts only when no other can), delivers one held send or steps
+ *   --write-micro FILE  with --micro-seed: after the run, write the schedule it followed as the
+ *       tokens --micro reads, so that `--micro FILE` writes the same dumps
+ *   --explore-micro K [--weights a,b,..]  --explore over seeded micro-step schedules, seeds S0 ..
+ *       S0 + K - 1 (S0 = --micro-seed, default 0) under one weight vector (dash_explore_micro);
+ *       same output lines (`--micro-seed <seed> --weights ...` then writes that state's dumps):
+ *       e.g. `test_4 --explore-micro 250 --weights 4,0,31,1` lists the accepted run_3
  *
  * Bulk modes (one GPU batch, many systems; dumps go to OUT_DIR/<k>/):
  *   --batch LIST        system k = the k-th trace directory listed in LIST (one per line)
@@ -142,11 +151,62 @@ static long read_micro(const char *path, unsigned n, uint8_t **out) {
     return rows;
 }
 
-/* dash_simulate_dir plus a schedule (seed, explicit rounds or micro-steps) and the event log of the
-   one system */
+/* --weights a,b,..: node t's weight in byte t. Returns 0, or -1 on a malformed list. */
+static int parse_weights(const char *text, unsigned n, uint64_t *out) {
+    uint64_t w = 0;
+    unsigned t = 0;
+    for (const char *p = text; *p; t++) {
+        char *e;
+        const unsigned long v = strtoul(p, &e, 10);
+        if (e == p || v > 31 || t >= n || (*e && *e != ',')) return -1;
+        w |= (uint64_t)v << (8 * t);
+        p = *e ? e + 1 : e;
+        if (*e == ',' && !*p) return -1;
+    }
+    if (t == 0) return -1;
+    *out = w;
+    return 0;
+}
+
+/* --write-micro FILE: the acts of the run under --micro-seed as --micro's tokens, P<t> / I<t> for a
+   step by the kind of the event it logged, D<t> for a delivery */
+static int write_micro(dash_t *h, const char *path, unsigned n) {
+    uint32_t rounds = 0, cap = 0, total = 0;
+    int rc = dash_read_micro_acts(h, 0, NULL, 0, &rounds);
+    if (rc != DASH_OK && !(rc == DASH_EINVAL && rounds)) return rc;
+    uint8_t *acts = (uint8_t *)malloc((size_t)rounds * n + 1);
+    dash_event *ev = NULL;
+    rc = acts ? dash_read_micro_acts(h, 0, acts, rounds, &rounds) : DASH_ENOMEM;
+    if (rc == DASH_OK) rc = dash_read_events(h, 0, NULL, 0, &cap);
+    if (rc == DASH_OK && !(ev = (dash_event *)malloc(sizeof *ev * (cap ? cap : 1)))) rc = DASH_ENOMEM;
+    if (rc == DASH_OK) rc = dash_read_events(h, 0, ev, cap, &total);
+    FILE *f = rc == DASH_OK ? fopen(path, "w") : NULL;
+    if (rc == DASH_OK && !f) rc = DASH_EIO;
+    uint32_t k = 0;
+    for (uint32_t r = 0; f && r < rounds; r++)
+        for (unsigned t = 0; t < n; t++) {
+            const uint8_t a = acts[(size_t)r * n + t];
+            if (a == DASH_SIT_OUT) continue;
+            char c = 'D';
+            if (a == DASH_MICRO_STEP) {  /* the step's event: one per stepping round, in round order */
+                if (k >= total || ev[k].round != r || ev[k].node != t) rc = DASH_EINVAL;
+                else c = ev[k].kind == DASH_EV_INSTR ? 'I' : 'P';
+                k++;
+            }
+            if (fprintf(f, "%c%u\n", c, t) < 0) rc = DASH_EIO;
+        }
+    if (f && fclose(f) != 0) rc = DASH_EIO;
+    free(ev);
+    free(acts);
+    return rc;
+}
+
+/* dash_simulate_dir plus a schedule (seed, explicit rounds, micro-steps, or a micro seed with its
+   weights) and the event log of the one system */
 static int simulate_traced(const char *dir, unsigned n, unsigned cs, unsigned m, const char *out, int dev,
                            int dbg_instr, int dbg_msg, unsigned long long sched, const uint8_t *rounds,
-                           long nrounds, int micro, dash_stats *st) {
+                           long nrounds, int micro, const uint64_t *mseed, uint64_t weights,
+                           const char *write_micro_file, dash_stats *st) {
     dash_cfg cfg = {0};
     cfg.num_procs = n;
     cfg.cache_size = cs;
@@ -158,13 +218,14 @@ static int simulate_traced(const char *dir, unsigned n, unsigned cs, unsigned m,
        up to 2^22): n x 4 B per round on the device */
     uint64_t log_rounds = 1024u + 256ull * m;
     if (log_rounds > (1u << 22)) log_rounds = 1u << 22;
-    cfg.trace_events = (dbg_instr || dbg_msg) ? (uint32_t)log_rounds : 0;
-    cfg.schedule_seed = rounds ? (sched ? sched : 1) : sched;
+    cfg.trace_events = (dbg_instr || dbg_msg || write_micro_file) ? (uint32_t)log_rounds : 0;
+    cfg.schedule_seed = (rounds || mseed) ? (sched ? sched : 1) : sched;
     dash_t *h = NULL;
     int rc = dash_create(&cfg, &h);
     if (rc != DASH_OK) return rc;
     if (rounds) rc = micro ? dash_set_micro_schedule(h, rounds, (uint32_t)nrounds)
                            : dash_set_schedule(h, rounds, (uint32_t)nrounds);
+    if (mseed) rc = dash_set_micro_seeds(h, mseed, &weights, 1);
     if (rc == DASH_OK && (rc = dash_load_dir(h, dir, 0)) == DASH_OK && (rc = dash_run(h, st)) == DASH_OK) {
         dash_node_state nodes[DASH_MAX_PROCS];
         rc = dash_read_state(h, 0, nodes);
@@ -175,7 +236,8 @@ static int simulate_traced(const char *dir, unsigned n, unsigned cs, unsigned m,
         }
         uint32_t cap = 0, total = 0;
         dash_event *ev = NULL;
-        if (rc == DASH_OK && cfg.trace_events) {  /* the count first, then the events */
+        if (rc == DASH_OK && write_micro_file) rc = write_micro(h, write_micro_file, n);
+        if (rc == DASH_OK && (dbg_instr || dbg_msg)) {  /* the count first, then the events */
             int erc = dash_read_events(h, 0, NULL, 0, &cap);
             if (erc == DASH_OK || erc == DASH_ETRUNC)
                 ev = (dash_event *)malloc(sizeof(dash_event) * (cap ? cap : 1));
@@ -218,9 +280,10 @@ static int write_rounds(const char *path, unsigned long long sched, unsigned n, 
     return rc;
 }
 
-/* --explore K: the distinct outcomes of K seeded schedules of one trace directory */
+/* --explore K / --explore-micro K (weights != NULL): the distinct outcomes of K seeded schedules of one
+   trace directory */
 static int explore_dir(const char *dir, unsigned n, unsigned cs, unsigned m, int dev, unsigned long long k,
-                       unsigned long long s0) {
+                       unsigned long long s0, const uint64_t *weights) {
     char base[4096], path[4200];
     int rc = dash_resolve_dir(dir, base, sizeof base);
     if (rc != DASH_OK || n < 1 || n > DASH_MAX_PROCS) {
@@ -253,12 +316,15 @@ static int explore_dir(const char *dir, unsigned n, unsigned cs, unsigned m, int
         uint32_t total = 0, cap = 256;
         dash_outcome *o = (dash_outcome *)malloc(cap * sizeof *o);
         if (!o) rc = DASH_ENOMEM;
-        else rc = dash_explore(h, 0, s0, k, o, cap, &total);
+        else rc = weights ? dash_explore_micro(h, 0, s0, k, *weights, o, cap, &total)
+                          : dash_explore(h, 0, s0, k, o, cap, &total);
         if (rc == DASH_OK && total > cap) { /* rare: once more, with room for all of them */
             cap = total;
             free(o);
             o = (dash_outcome *)malloc((size_t)cap * sizeof *o);
-            rc = o ? dash_explore(h, 0, s0, k, o, cap, &total) : DASH_ENOMEM;
+            rc = !o ? DASH_ENOMEM
+                 : weights ? dash_explore_micro(h, 0, s0, k, *weights, o, cap, &total)
+                           : dash_explore(h, 0, s0, k, o, cap, &total);
         }
         for (uint32_t i = 0; rc == DASH_OK && i < total && i < cap; i++)
             printf("%016llx %llu %llu %u %x\n", (unsigned long long)o[i].digest, (unsigned long long)o[i].count,
@@ -376,9 +442,10 @@ int main(int argc, char *argv[]) {
     unsigned n = 4, cs = 4, m = 32;
     int dev = 0, show = 0, dbg_instr = 0, dbg_msg = 0, n_given = 0, device_ingest = 0;
     const char *out = ".", *dir = NULL, *batch = NULL, *digests = NULL, *dump = NULL, *rounds_file = NULL,
-               *micro_file = NULL, *write_rounds_file = NULL;
-    unsigned long long synth = 0, seed = 0x5EED, sched = 0, explore = 0;
-    int explore_given = 0;
+               *micro_file = NULL, *write_rounds_file = NULL, *write_micro_file = NULL, *weights_text = NULL;
+    unsigned long long synth = 0, seed = 0x5EED, sched = 0, explore = 0, micro_seed = 0;
+    int explore_given = 0, explore_micro = 0, micro_seed_given = 0;
+    uint64_t weights = DASH_MICRO_UNIFORM;
     unsigned len = 4096, kind = DASH_GEN_UNIFORM;
     double loc = 0.5;
     for (int i = 1; i < argc; i++) {
@@ -402,6 +469,11 @@ int main(int argc, char *argv[]) {
         else if (!strcmp(argv[i], "--micro") && i + 1 < argc) micro_file = argv[++i];
         else if (!strcmp(argv[i], "--write-rounds") && i + 1 < argc) write_rounds_file = argv[++i];
         else if (!strcmp(argv[i], "--explore") && i + 1 < argc) explore = strtoull(argv[++i], NULL, 0), explore_given = 1;
+        else if (!strcmp(argv[i], "--explore-micro") && i + 1 < argc)
+            explore = strtoull(argv[++i], NULL, 0), explore_given = explore_micro = 1;
+        else if (!strcmp(argv[i], "--micro-seed") && i + 1 < argc) micro_seed = strtoull(argv[++i], NULL, 0), micro_seed_given = 1;
+        else if (!strcmp(argv[i], "--weights") && i + 1 < argc) weights_text = argv[++i];
+        else if (!strcmp(argv[i], "--write-micro") && i + 1 < argc) write_micro_file = argv[++i];
         else if (!strcmp(argv[i], "--locality") && i + 1 < argc) loc = atof(argv[++i]);
         else if (!strcmp(argv[i], "--kind") && i + 1 < argc) {
             const char *k = argv[++i];
@@ -422,12 +494,21 @@ int main(int argc, char *argv[]) {
         fprintf(stderr, "Usage: %s <test_directory>\n", argv[0]); /* ref :128 */
         return EXIT_FAILURE;
     }
+    if (weights_text && parse_weights(weights_text, n, &weights) != 0) {
+        fprintf(stderr, "cache_simulator: --weights: up to %u comma-separated weights of 0..31\n", n);
+        return EXIT_FAILURE;
+    }
+    if (weights_text && !explore_micro && !micro_seed_given) {
+        fprintf(stderr, "cache_simulator: --weights goes with --micro-seed or --explore-micro\n");
+        return EXIT_FAILURE;
+    }
     if (explore_given) {
-        if (rounds_file || micro_file || write_rounds_file) {
-            fprintf(stderr, "cache_simulator: --explore takes no --rounds, --micro or --write-rounds\n");
+        if (rounds_file || micro_file || write_rounds_file || write_micro_file) {
+            fprintf(stderr, "cache_simulator: --explore takes no --rounds, --micro, --write-rounds or --write-micro\n");
             return EXIT_FAILURE;
         }
-        int rc = explore_dir(dir, n, cs, m, dev, explore, sched);
+        int rc = explore_dir(dir, n, cs, m, dev, explore, explore_micro ? micro_seed : sched,
+                             explore_micro ? &weights : NULL);
         if (rc != DASH_OK) {
             const char *why = dash_last_error(NULL);
             fprintf(stderr, "cache_simulator: %s (%d)\n", why[0] ? why : "failed", rc);
@@ -436,6 +517,15 @@ int main(int argc, char *argv[]) {
     }
     if (write_rounds_file && (rounds_file || micro_file)) {  /* the file would restate the seed, not the run */
         fprintf(stderr, "cache_simulator: --write-rounds goes with --schedule, not with --rounds or --micro\n");
+        return EXIT_FAILURE;
+    }
+    if (micro_seed_given && (rounds_file || micro_file || sched || write_rounds_file)) {
+        fprintf(stderr, "cache_simulator: --micro-seed is a schedule of its own: no --schedule, --rounds, --micro "
+                        "or --write-rounds\n");
+        return EXIT_FAILURE;
+    }
+    if (write_micro_file && !micro_seed_given) {
+        fprintf(stderr, "cache_simulator: --write-micro goes with --micro-seed\n");
         return EXIT_FAILURE;
     }
     uint8_t *rounds = NULL;
@@ -456,9 +546,11 @@ int main(int argc, char *argv[]) {
         return EXIT_FAILURE;
     }
     dash_stats st;
-    int rc = (dbg_instr || dbg_msg || sched || rounds || write_rounds_file)
+    const uint64_t mseed = micro_seed;
+    int rc = (dbg_instr || dbg_msg || sched || rounds || write_rounds_file || micro_seed_given)
                  ? simulate_traced(dir, n, cs, m, out, dev, dbg_instr, dbg_msg, sched, rounds, nrounds,
-                                   micro_file != NULL, &st)
+                                   micro_file != NULL, micro_seed_given ? &mseed : NULL, weights, write_micro_file,
+                                   &st)
                  : dash_simulate_dir(dir, n, cs, m, out, dev, &st);
     free(rounds);
     if (rc == DASH_OK && write_rounds_file &&

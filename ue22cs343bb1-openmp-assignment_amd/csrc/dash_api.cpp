@@ -49,6 +49,8 @@ struct dash_ctx {
     bool micro = false;                 // the round table is a micro-step schedule (MODE 4)
     uint64_t* d_seeds = nullptr;        // [num_systems] per-system schedule seeds (dash_set_system_seeds)
     bool per_sys = false;               // the runs follow d_seeds, not the round table
+    uint64_t* d_mseeds = nullptr;       // [num_systems][2] seed, weights (dash_set_micro_seeds)
+    bool micro_sys = false;             // the runs follow d_mseeds: a seeded micro-step schedule each
     bool tab_custom = false;            // the round table holds an explicit schedule, not the handle seed's
     uint32_t* d_event_count = nullptr;  // [sys*N+node]
     uint32_t ev_rounds = 0;             // trace_events rounded up to a multiple of 4
@@ -168,6 +170,7 @@ static void release(dash_t* h) {
     (void)hipFree(h->d_skip);
     (void)hipFree(h->d_arb);
     (void)hipFree(h->d_seeds);
+    (void)hipFree(h->d_mseeds);
     (void)hipFree(h->d_text);
     (void)hipFree(h->d_foff);
     (void)hipFree(h->d_flen);
@@ -419,6 +422,7 @@ int dash_set_schedule(dash_t* h, const uint8_t* sched, uint32_t rounds) {
         h->ran = false;
         h->micro = false;
         h->per_sys = false;
+        h->micro_sys = false;
         h->tab_custom = true;
         return DASH_OK;
     });
@@ -460,6 +464,7 @@ int dash_set_micro_schedule(dash_t* h, const uint8_t* acts, uint32_t rounds) {
         h->ran = false;
         h->micro = true;
         h->per_sys = false;
+        h->micro_sys = false;
         h->tab_custom = true;
         return DASH_OK;
     });
@@ -480,6 +485,7 @@ int dash_set_system_seeds(dash_t* h, const uint64_t* seeds, uint64_t n) {
             if (h->per_sys) HIPCHK(h, reset_hint(h));
             HIPCHK(h, hipStreamSynchronize(h->stream));
             h->per_sys = false;
+            h->micro_sys = false;
             h->ran = false;
             return DASH_OK;
         }
@@ -499,7 +505,91 @@ int dash_set_system_seeds(dash_t* h, const uint64_t* seeds, uint64_t n) {
         HIPCHK(h, reset_hint(h));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         h->per_sys = true;
+        h->micro_sys = false;
         h->ran = false;
+        return DASH_OK;
+    });
+}
+
+int dash_set_micro_seeds(dash_t* h, const uint64_t* seeds, const uint64_t* weights, uint64_t n) {
+    return guarded(h, "dash_set_micro_seeds", [&]() -> int {
+        if (!h) return DASH_EINVAL;
+        if (!h->d_arb) return fail(h, DASH_ESTATE, "dash_set_micro_seeds: handle created with schedule_seed = 0");
+        HIPCHK(h, hipSetDevice(h->cfg.device));
+        if (!seeds) {  // back to the handle's own seed and its round table
+            if (n) return fail(h, DASH_EINVAL, "dash_set_micro_seeds: null seeds with n = %llu", (unsigned long long)n);
+            if (h->tab_custom) {  // dash_set_schedule / dash_set_micro_schedule overwrote the table
+                HIPCHK(h, dash::launch_arb_table(h->cfg.schedule_seed, h->seg, h->d_arb, h->arb_len, h->stream));
+                h->tab_custom = false;
+            }
+            HIPCHK(h, reset_hint(h));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            h->micro = h->per_sys = h->micro_sys = false;
+            h->ran = false;
+            return DASH_OK;
+        }
+        if (n != h->cfg.num_systems)
+            return fail(h, DASH_EINVAL, "dash_set_micro_seeds: %llu seeds for %llu systems", (unsigned long long)n,
+                        (unsigned long long)h->cfg.num_systems);
+        std::vector<uint64_t> pairs(2 * n);
+        for (uint64_t k = 0; k < n; k++) {
+            const uint64_t w = weights ? weights[k] : DASH_MICRO_UNIFORM;
+            if (w & 0xE0E0E0E0E0E0E0E0ull)
+                return fail(h, DASH_EINVAL, "dash_set_micro_seeds: system %llu: a weight above 31", (unsigned long long)k);
+            pairs[2 * k] = seeds[k];
+            pairs[2 * k + 1] = w;
+        }
+        if (!h->d_mseeds) {
+            hipError_t e = hipMalloc(&h->d_mseeds, std::max<uint64_t>(n, 1) * 2 * sizeof(uint64_t));
+            if (e != hipSuccess) {
+                h->d_mseeds = nullptr;
+                return fail(h, e == hipErrorOutOfMemory ? DASH_ENOMEM : DASH_EDEVICE, "hipMalloc(micro seeds): %s",
+                            hipGetErrorString(e));
+            }
+        }
+        if (n) HIPCHK(h, hipMemcpyAsync(h->d_mseeds, pairs.data(), pairs.size() * sizeof(uint64_t),
+                                        hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, reset_hint(h));  // micro-step runs take no tiers: the hint of earlier runs is void
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        h->micro = h->per_sys = false;
+        h->micro_sys = true;
+        h->ran = false;
+        return DASH_OK;
+    });
+}
+
+int dash_read_micro_acts(dash_t* h, uint64_t sys, uint8_t* acts, uint32_t cap_rounds, uint32_t* rounds) {
+    return guarded(h, "dash_read_micro_acts", [&]() -> int {
+        if (!h || !rounds || (!acts && cap_rounds)) return DASH_EINVAL;
+        *rounds = 0;
+        if (!h->micro_sys) return fail(h, DASH_ESTATE, "dash_read_micro_acts: no micro seeds set");
+        if (!h->d_events) return fail(h, DASH_ESTATE, "dash_read_micro_acts: created with trace_events = 0");
+        if (!h->ran) return fail(h, DASH_ESTATE, "dash_run has not completed");
+        if (sys >= h->cfg.num_systems) return fail(h, DASH_EINVAL, "system out of range");
+        const uint32_t N = h->cfg.num_procs, R = h->ev_rounds;
+        uint32_t sys_rounds = 0;
+        HIPCHK(h, hipSetDevice(h->cfg.device));
+        HIPCHK(h, hipMemcpyAsync(&sys_rounds, h->d_rounds + sys, 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        *rounds = sys_rounds;
+        if (sys_rounds > R)
+            return fail(h, DASH_ETRUNC, "dash_read_micro_acts: the run took %u rounds, the log holds %u", sys_rounds, R);
+        if (sys_rounds > cap_rounds)
+            return fail(h, DASH_EINVAL, "dash_read_micro_acts: %u rounds > cap_rounds %u", sys_rounds, cap_rounds);
+        const uint32_t Rs = (sys_rounds + 3u) & ~3u;  // whole 4-round rows; <= R, a multiple of 4
+        std::vector<uint32_t> ev((size_t)N * Rs);
+        if (Rs) {
+            HIPCHK(h, hipMemcpyAsync(ev.data(), h->d_events + sys * N * (uint64_t)R, ev.size() * 4, hipMemcpyDeviceToHost,
+                                     h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+        }
+        // a round's acting node left an event word (bit 24: it stepped) or the delivery marker
+        for (uint32_t r = 0; r < sys_rounds; r++)
+            for (uint32_t t = 0; t < N; t++) {
+                const uint32_t w = ev[(size_t)(r / 4) * N * 4 + t * 4 + r % 4];
+                acts[(uint64_t)r * N + t] = (w & 0x01000000u) ? DASH_MICRO_STEP : w == 0x02000000u ? DASH_MICRO_SEND
+                                                                                                    : DASH_SIT_OUT;
+            }
         return DASH_OK;
     });
 }
@@ -517,18 +607,21 @@ int dash_broadcast_system(dash_t* h, uint64_t src) {
     return DASH_OK;
 }
 
-int dash_explore(dash_t* h, uint64_t src, uint64_t first_seed, uint64_t num_seeds, dash_outcome* out, uint32_t cap,
-                 uint32_t* n) {
-    return guarded(h, "dash_explore", [&]() -> int {
+// dash_explore and dash_explore_micro: broadcast, passes of num_systems seeds, the merge of their
+// outcomes. weights == nullptr: seeded round schedules (dash_set_system_seeds); else seeded
+// micro-step schedules under that one weight vector (dash_set_micro_seeds).
+static int explore_impl(dash_t* h, const char* what, uint64_t src, uint64_t first_seed, uint64_t num_seeds,
+                        const uint64_t* weights, dash_outcome* out, uint32_t cap, uint32_t* n) {
+    return guarded(h, what, [&]() -> int {
         if (!h || !n || (!out && cap)) return DASH_EINVAL;
         *n = 0;
         const uint64_t nsys = h->cfg.num_systems;
-        if (!h->d_arb) return fail(h, DASH_ESTATE, "dash_explore: handle created with schedule_seed = 0");
-        if (h->micro) return fail(h, DASH_ESTATE, "dash_explore: the handle follows a micro-step schedule");
-        if (num_seeds && !nsys) return fail(h, DASH_EINVAL, "dash_explore: the handle has no systems");
+        if (!h->d_arb) return fail(h, DASH_ESTATE, "%s: handle created with schedule_seed = 0", what);
+        if (!weights && h->micro) return fail(h, DASH_ESTATE, "%s: the handle follows a micro-step schedule", what);
+        if (num_seeds && !nsys) return fail(h, DASH_EINVAL, "%s: the handle has no systems", what);
         int rc = dash_broadcast_system(h, src);
         if (rc != DASH_OK) return rc;
-        std::vector<uint64_t> seeds(nsys), dig(nsys);
+        std::vector<uint64_t> seeds(nsys), dig(nsys), wts(weights ? nsys : 0, weights ? *weights : 0);
         std::vector<uint32_t> rnd(nsys), err(nsys);
         std::vector<dash_outcome> found;
         std::map<std::pair<uint64_t, uint32_t>, size_t> index;  // (digest, errors) -> found[]
@@ -536,7 +629,9 @@ int dash_explore(dash_t* h, uint64_t src, uint64_t first_seed, uint64_t num_seed
             const uint64_t fresh = std::min<uint64_t>(nsys, num_seeds - base);
             // the last pass pads with repeats of its own seeds, which are not counted
             for (uint64_t i = 0; i < nsys; i++) seeds[i] = first_seed + base + i % fresh;
-            if ((rc = dash_set_system_seeds(h, seeds.data(), nsys)) != DASH_OK) return rc;
+            rc = weights ? dash_set_micro_seeds(h, seeds.data(), wts.data(), nsys)
+                         : dash_set_system_seeds(h, seeds.data(), nsys);
+            if (rc != DASH_OK) return rc;
             if ((rc = dash_run(h, nullptr)) != DASH_OK) return rc;
             if ((rc = dash_read_results(h, 0, nsys, dig.data(), rnd.data(), err.data())) != DASH_OK) return rc;
             for (uint64_t i = 0; i < fresh; i++) {
@@ -555,6 +650,17 @@ int dash_explore(dash_t* h, uint64_t src, uint64_t first_seed, uint64_t num_seed
         for (size_t k = 0; k < found.size() && k < cap; k++) out[k] = found[k];
         return DASH_OK;
     });
+}
+
+int dash_explore(dash_t* h, uint64_t src, uint64_t first_seed, uint64_t num_seeds, dash_outcome* out, uint32_t cap,
+                 uint32_t* n) {
+    return explore_impl(h, "dash_explore", src, first_seed, num_seeds, nullptr, out, cap, n);
+}
+
+int dash_explore_micro(dash_t* h, uint64_t src, uint64_t first_seed, uint64_t num_seeds, uint64_t weights,
+                       dash_outcome* out, uint32_t cap, uint32_t* n) {
+    if (h && (weights & 0xE0E0E0E0E0E0E0E0ull)) return fail(h, DASH_EINVAL, "dash_explore_micro: a weight above 31");
+    return explore_impl(h, "dash_explore_micro", src, first_seed, num_seeds, &weights, out, cap, n);
 }
 
 int dash_run(dash_t* h, dash_stats* stats) {
@@ -582,6 +688,11 @@ int dash_run(dash_t* h, dash_stats* stats) {
         a.arb_tab = reinterpret_cast<const uint32_t*>(h->d_seeds);
         a.arb_len = 0;
     }
+    if (h->micro_sys) {  // seeded micro-step schedules: MODE 4 with no table, (seed, weights) pairs instead
+        a.micro = 1u;
+        a.arb_tab = reinterpret_cast<const uint32_t*>(h->d_mseeds);
+        a.arb_len = 0;
+    }
     a.cache_size = h->cfg.cache_size;
     for (uint32_t b = 0; b < 16; b++)  // b % CACHE_SIZE for the generic (non-power-of-two) kernels
         a.cs_lut |= (uint64_t)(b % h->cfg.cache_size) << (4 * b);
@@ -601,7 +712,7 @@ int dash_run(dash_t* h, dash_stats* stats) {
     const uint32_t* list = nullptr;
     const uint32_t f = h->cfg.flags;
     // a micro-step schedule runs at the reference's queue depth only (sim_kernel MODE 4)
-    const int first = (h->micro || (f & DASH_TIER_FROM_256)) ? 2 : (f & DASH_TIER_FROM_32) ? 1 : h->auto_tier;
+    const int first = (h->micro || h->micro_sys || (f & DASH_TIER_FROM_256)) ? 2 : (f & DASH_TIER_FROM_32) ? 1 : h->auto_tier;
     if (h->hint_n && h->hint_tier != first) HIPCHK(h, reset_hint(h));
     // Systems that overflowed the first tier in an earlier run of these traces (the
     // schedule is deterministic, so they will again) start one tier deeper on the side

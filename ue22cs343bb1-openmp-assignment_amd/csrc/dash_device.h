@@ -57,7 +57,9 @@ struct SimArgs {
                               // (>= 4 for any table). 0: per-system seeds (dash_set_system_seeds),
                               // arb_tab points at uint64_t seeds[nsys] and arb_seed only selects
                               // the seeded kernel
-    uint32_t micro;           // 1: arb_tab is a micro-step table (dash_set_micro_schedule, MODE 4)
+    uint32_t micro;           // 1: arb_tab is a micro-step table (dash_set_micro_schedule, MODE 4); with
+                              // arb_len == 0 (dash_set_micro_seeds) it points at uint64_t
+                              // {seed, weights}[nsys], a seeded micro-step schedule per system
     const uint8_t* skip;      // optional [sys]: 1 = run elsewhere this pass (a deeper tier, concurrently)
     uint32_t cache_size;      // CACHE_SIZE (ref :7); read by the generic (non-power-of-two) kernels
     uint64_t cs_lut;          // nibble b = b % cache_size, b < 16 (generic kernels)

@@ -225,3 +225,26 @@ int dash_seed_schedule(uint64_t seed, uint32_t num_procs, uint32_t rounds, uint8
     }
     return DASH_OK;
 }
+
+/* The seeded micro-step schedule's pick (include/dash.h states the rule; the kernel's twin is
+   micro_pick_lane in csrc/dash_kernels.hip). */
+int dash_micro_pick(uint64_t seed, uint32_t round, uint32_t enabled, uint64_t weights, uint32_t num_procs) {
+    if (num_procs < 1 || num_procs > DASH_MAX_PROCS || enabled == 0 || (enabled >> num_procs) != 0)
+        return DASH_EINVAL;
+    for (uint32_t t = 0; t < 8; t++)
+        if (((weights >> (8 * t)) & 0xFFu) > 31u) return DASH_EINVAL;
+    uint32_t W = 0;
+    for (uint32_t t = 0; t < num_procs; t++)
+        if ((enabled >> t) & 1u) W += (uint32_t)(weights >> (8 * t)) & 0xFFu;
+    const int flat = W == 0; /* only weight-0 nodes are enabled: they count 1 each */
+    if (flat) W = (uint32_t)__builtin_popcount(enabled);
+    const uint64_t u = fmix64(seed ^ ((uint64_t)round * 0x9E3779B97F4A7C15ULL)) >> 32;
+    const uint32_t x = (uint32_t)((u * W) >> 32);
+    uint32_t acc = 0;
+    for (uint32_t t = 0; t < num_procs; t++) {
+        if (!((enabled >> t) & 1u)) continue;
+        acc += flat ? 1u : (uint32_t)(weights >> (8 * t)) & 0xFFu;
+        if (acc > x) return (int)t;
+    }
+    return DASH_EINVAL; /* not reached: x < W */
+}

@@ -118,6 +118,29 @@ __device__ __forceinline__ uint32_t arb_lane(uint64_t seed, uint32_t round, uint
     return (!lock && ((uint32_t)(skey >> (8 * t)) & 3u) == 0) ? 0u : 2u << (4u * pos);
 }
 
+// The seeded micro-step schedule's pick (include/dash.h states the rule; host twin dash_micro_pick):
+// the node that acts in `round` of the system whose enabled nodes are the bits of `en` (all below
+// P), by the system's seed and weight bytes; the result is no node of the system when en == 0.
+// Per lane on the vector unit, as arb_lane: a wave's systems differ in seed, weights and state.
+template <uint32_t P>
+__device__ __forceinline__ uint32_t micro_pick_lane(uint64_t seed, uint64_t wts, uint32_t round, uint32_t en) {
+    constexpr uint64_t ONES = 0x0101010101010101ull;
+    // byte t = 1 when node t is enabled: en's bit t alone in byte t, then any set bit to bit 0
+    const uint64_t eb = (((((uint64_t)en * ONES) & 0x8040201008040201ull) + 0x7F7F7F7F7F7F7F7Full) >> 7) & ONES;
+    uint64_t mw = wts & (eb * 0xFFull);  // the enabled nodes' weights (each <= 31)
+    mw = mw ? mw : eb;                   // W == 0: every enabled node counts 1
+    const uint64_t cum = mw * ONES;      // byte t = the inclusive weight sum (<= 248: no carries)
+    const uint32_t W = (uint32_t)(cum >> 56);
+    const uint32_t u = (uint32_t)(fmix64(seed ^ ((uint64_t)round * 0x9E3779B97F4A7C15ull)) >> 32);
+    const uint32_t x = __umulhi(u, W);
+    // the sums never fall and the last is W > x: the lowest node whose sum exceeds x is the
+    // number of sums that do not (its own weight is positive, so it is enabled)
+    uint32_t pick = 0;
+#pragma unroll
+    for (uint32_t t = 0; t < P; ++t) pick += ((uint32_t)(cum >> (8 * t)) & 0xFFu) <= x ? 1u : 0u;
+    return pick;
+}
+
 // CS = CACHE_SIZE; CS = 0 is the generic kernel for a non-power-of-two CACHE_SIZE (read at
 // run time, LDS sized for the maximum of 16 lines)
 template <int CS>
@@ -190,7 +213,9 @@ __device__ __forceinline__ mask_t Mbit15(uint32_t v) {
 //   4 = an explicit micro-step schedule with the event log (a.micro, dash_set_micro_schedule): per
 //       round one node either steps, holding its sends in an LDS outbox, or delivers its oldest
 //       held message -- the reference's threads interleaved at sendMessage granularity, as in
-//       the oracle's STRICT model (queue depth 256 only).
+//       the oracle's STRICT model (queue depth 256 only); with a.arb_len == 0 every system follows
+//       a seeded micro-step schedule of its own (dash_set_micro_seeds): each round one of its
+//       enabled nodes, picked by the system's seed and weights (micro_pick_lane), acts.
 // Mode 1 without the event-log code keeps its loop free of SGPR spill reloads; the schedule is a
 // compile-time property of every mode (a run-time test in the event-log kernel cost it 12 %).
 template <int P, int CS, uint32_t RING, int MODE>
@@ -387,6 +412,14 @@ void sim_kernel(const SimArgs a) {
         const uint64_t sd = live ? reinterpret_cast<const uint64_t*>(a.arb_tab)[sys] : 0ull;
         arbn = make_uint4((uint32_t)sd, (uint32_t)(sd >> 32), 0u, 0u);
     }
+    // seeded micro-step schedules (dash_set_micro_seeds): the same convention, and arb_tab holds
+    // one (seed, weights) pair per system; arbn carries both
+    if constexpr (MICRO) {
+        if (a.arb_len == 0u) {
+            COLD();
+            arbn = live ? reinterpret_cast<const uint4*>(a.arb_tab)[sys] : make_uint4(0, 0, 0, 0);
+        }
+    }
 
     // Every predicate of a step is a wave-wide lane mask (an SGPR pair): one compare makes
     // it, the scalar unit combines them, v_cndmask consumes them. The kernel is bound by
@@ -413,6 +446,16 @@ void sim_kernel(const SimArgs a) {
             // primary arrival bit
             wp = k == 0 ? arbw.x : k == 1 ? arbw.y : k == 2 ? arbw.z : arbw.w;
             if constexpr (MICRO) {  // 1: the node steps (its sends are held), 2: it sends one held message
+                if (a.arb_len == 0u) {
+                    // seeded micro-step schedule: the word comes from the round's own state -- of the
+                    // system's enabled nodes (held sends, a queue to pop, an instruction to issue)
+                    // the picked one acts: it sends if it holds sends, else it steps
+                    COLD();
+                    const uint32_t en = (uint32_t)((mMsg | mIss | held()) >> seg) & SEGMASK;
+                    const uint32_t pick = micro_pick_lane<P>((uint64_t)arbn.x | ((uint64_t)arbn.y << 32),
+                                                             (uint64_t)arbn.z | ((uint64_t)arbn.w << 32), rv + k, en);
+                    wp = (t == pick && ((en >> t) & 1u)) ? (on != 0u ? 2u : 1u) : 0u;
+                }
                 mStall = M(wp != 1u);
                 bitI = 1u;
             } else {
@@ -473,7 +516,14 @@ void sim_kernel(const SimArgs a) {
             // instruction in bits 0..15
             const uint32_t evx = B(mHas) ? ((m & 0x70FFFFFFu) | 0x01000000u) : B(mDo) ? (ins | 0x81000000u) : 0u;
             // (named words, not an array indexed by k % 4: the fast kernel's code stays the same)
-            (k % 4u == 0u ? ev0 : k % 4u == 1u ? ev1 : k % 4u == 2u ? ev2 : ev3) = evx;
+            uint32_t evw = evx;
+            if constexpr (MICRO) {
+                // a seeded micro-step schedule records its deliveries too: a marker in the sender's
+                // slot, an encoding no event has (bit 24 clear; not counted, dash_read_events skips
+                // it), so the log holds the whole schedule (dash_read_micro_acts)
+                if (a.arb_len == 0u) evw = wp == 2u ? 0x02000000u : evx;
+            }
+            (k % 4u == 0u ? ev0 : k % 4u == 1u ? ev1 : k % 4u == 2u ? ev2 : ev3) = evw;
             nev += B(mHas | mDo) ? 1u : 0u;
         }
         // messages handled per transactionType, per system; a lane without a message counts
@@ -632,6 +682,19 @@ void sim_kernel(const SimArgs a) {
             }
             if (B(mVP)) push(wP, dP);
             if (B(mVB)) push(wA, msr);
+            // a seeded schedule holds an eviction notice to a node >= N too (flagged and counted
+            // above): its sendMessage call is a micro-step of the thread like any other (the
+            // oracle's STRICT model drops it at its SEND), so the node stays enabled as a sender
+            // and the notice is dropped by its delivery below. No handler sends both this and
+            // mVP's message, and it is the step's last send. A table-driven run keeps dropping it
+            // at the step: there the notice's SEND act finds the outbox empty and does nothing.
+            // DASH_ERR_OOB and `drops` are raised at the step in both (the oracle raises them at
+            // the SEND): the same at the end of a completed run, one act early for a system the
+            // round cap stops while it still holds the notice.
+            if (a.arb_len == 0u && mOob != 0) {
+                COLD();
+                if (B(mOob)) push(wE, dE);
+            }
             if (mBad != 0) {  // the pushes above stayed in this lane's own outbox column
                 COLD();
                 err |= B(mBad) ? DASH_ERR_SCHEDULE_D : 0u;
@@ -648,7 +711,7 @@ void sim_kernel(const SimArgs a) {
             xwP = lds[L::WORDS + oh * 128u + lane];
             oh = snd ? (oh + 1u) & (OUTBOX - 1u) : oh;
             on -= snd ? 1u : 0u;
-            xVP = M(snd);
+            xVP = M(snd && xdP < N);  // a held notice to a node >= N (seeded schedules) leaves and is dropped
             xVB = 0;
             xRID = 0;
         }

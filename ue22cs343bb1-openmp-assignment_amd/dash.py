@@ -13,6 +13,7 @@ libdash:
     Engine.load_dirs(dirs, device) -> bulk directory ingest, parsed on the host or the GPU
     Engine.run()                   -> the OpenMP parallel region (:149-738)
     Engine.explore(src, s0, k)     -> the outcomes k seeded legal schedules of one system reach
+    Engine.explore_micro(src, s0, k, weights) -> the same over seeded micro-step schedules
     Engine.read_state(sys)         -> the nodes' processorNode state
     dump_node(state, node)         -> printProcessorState bytes (:868-902)
     simulate_dir(dir, out_dir)     -> main() end to end
@@ -60,10 +61,12 @@ EXPORTS = ("dash_create", "dash_destroy", "dash_last_error", "dash_load_traces",
            "dash_write_digests", "dash_run_host_batched", "dash_set_schedule", "dash_probe_box",
            "dash_set_micro_schedule", "dash_parse_core_text", "dash_read_dirs_text", "dash_load_text",
            "dash_load_dirs_device", "dash_read_traces", "dash_ingest_info", "dash_set_system_seeds",
-           "dash_broadcast_system", "dash_seed_schedule", "dash_explore")
+           "dash_broadcast_system", "dash_seed_schedule", "dash_explore", "dash_micro_pick",
+           "dash_set_micro_seeds", "dash_read_micro_acts", "dash_explore_micro")
 TEXT_TILE = 4096  # DASH_TEXT_TILE: bytes per tile of the device text parser
 SIT_OUT = 0xFF
 MICRO_STEP, MICRO_SEND = 0, 1  # dash_set_micro_schedule actions
+MICRO_UNIFORM = 0x0101010101010101  # DASH_MICRO_UNIFORM: every node weight 1
 
 
 class DashError(RuntimeError):
@@ -192,6 +195,10 @@ def lib() -> ctypes.CDLL:
         "dash_broadcast_system": (i32, [vp, u64]),
         "dash_seed_schedule": (i32, [u64, u32, u32, vp]),
         "dash_explore": (i32, [vp, u64, u64, u64, vp, u32, ctypes.POINTER(u32)]),
+        "dash_micro_pick": (i32, [u64, u32, u32, u64, u32]),
+        "dash_set_micro_seeds": (i32, [vp, vp, vp, u64]),
+        "dash_read_micro_acts": (i32, [vp, u64, vp, u32, ctypes.POINTER(u32)]),
+        "dash_explore_micro": (i32, [vp, u64, u64, u64, u64, vp, u32, ctypes.POINTER(u32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -310,6 +317,27 @@ def seed_schedule(seed: int, num_procs: int, rounds: int) -> np.ndarray:
     buf = sched if rounds and num_procs else np.zeros(1, dtype=np.uint8)
     _check(lib().dash_seed_schedule(seed, num_procs, rounds, buf.ctypes.data), "dash_seed_schedule")
     return sched
+
+
+def pack_weights(weights) -> int:
+    """Per-node weights (each 0..31, node t first) as dash_set_micro_seeds' 64-bit vector; None =
+    uniform; an int is passed through."""
+    if weights is None:
+        return MICRO_UNIFORM
+    if isinstance(weights, (int, np.integer)):
+        return int(weights)
+    w = [int(x) for x in weights]
+    if len(w) > MAX_PROCS or any(x < 0 or x > 255 for x in w):
+        raise ValueError("weights: at most 8 values of one byte each")
+    return sum(x << (8 * t) for t, x in enumerate(w))
+
+
+def micro_pick(seed: int, round: int, enabled: int, weights, num_procs: int) -> int:
+    """dash_micro_pick: the node that acts in `round` of the seeded micro-step schedule (seed,
+    weights) when the nodes in the bit set `enabled` are enabled."""
+    t = lib().dash_micro_pick(seed, round, enabled, pack_weights(weights), num_procs)
+    _check(t if t < 0 else OK, "dash_micro_pick")
+    return t
 
 
 def probe_box(device=0) -> dict:
@@ -475,6 +503,46 @@ class Engine:
         assert seeds.ndim == 1
         _check(lib().dash_set_system_seeds(self.h, seeds.ctypes.data, len(seeds)), "dash_set_system_seeds", self.h)
 
+    def set_micro_seeds(self, seeds, weights=None, weights_per_system=None):
+        """dash_set_micro_seeds: system k follows the seeded micro-step schedule of seeds[k] under
+        its weight vector. weights: one vector for every system, a sequence of per-node weights or a
+        packed int (pack_weights); weights_per_system: one packed uint64 per system instead; neither
+        = uniform. seeds None returns the handle to its own seed. Needs schedule_seed != 0."""
+        if seeds is None:
+            _check(lib().dash_set_micro_seeds(self.h, None, None, 0), "dash_set_micro_seeds", self.h)
+            return
+        if weights is not None and weights_per_system is not None:
+            raise ValueError("set_micro_seeds: weights or weights_per_system, not both")
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        assert seeds.ndim == 1
+        if weights is not None:
+            weights_per_system = np.full(len(seeds), pack_weights(weights), dtype=np.uint64)
+        wp = None
+        if weights_per_system is not None:
+            weights_per_system = np.ascontiguousarray(weights_per_system, dtype=np.uint64)
+            assert weights_per_system.shape == seeds.shape
+            wp = weights_per_system.ctypes.data
+        _check(lib().dash_set_micro_seeds(self.h, seeds.ctypes.data, wp, len(seeds)), "dash_set_micro_seeds", self.h)
+
+    def read_micro_acts(self, sys: int) -> np.ndarray:
+        """dash_read_micro_acts: the schedule system `sys` followed in the last run under micro
+        seeds, uint8 [rounds][num_procs] as set_micro_schedule takes it (needs trace_events)."""
+        n = ctypes.c_uint32()
+        rc = lib().dash_read_micro_acts(self.h, sys, None, 0, ctypes.byref(n))
+        if rc != EINVAL or n.value == 0:  # EINVAL with the rounds set: the table's size
+            _check(rc, "dash_read_micro_acts", self.h)
+        acts = np.zeros((n.value, self.num_procs), dtype=np.uint8)
+        if n.value:
+            _check(lib().dash_read_micro_acts(self.h, sys, acts.ctypes.data, n.value, ctypes.byref(n)),
+                   "dash_read_micro_acts", self.h)
+        return acts
+
+    def explore_micro(self, src: int, first_seed: int, num_seeds: int, weights=None, cap=None) -> list:
+        """dash_explore_micro: explore() over seeded micro-step schedules, seeds first_seed + i under
+        one weight vector (None = uniform)."""
+        return self._explore(lib().dash_explore_micro, "dash_explore_micro", cap, src, first_seed, num_seeds,
+                             pack_weights(weights))
+
     def broadcast_system(self, src: int):
         """dash_broadcast_system: every system becomes a copy of system src (on the device)."""
         _check(lib().dash_broadcast_system(self.h, src), "dash_broadcast_system", self.h)
@@ -484,12 +552,14 @@ class Engine:
         num_seeds, as dicts (digest, count, seed = the lowest seed that reached it, rounds and errors
         of that witness), in witness-seed order. cap=k returns the first k; the total is
         explore_total afterwards either way."""
+        return self._explore(lib().dash_explore, "dash_explore", cap, src, first_seed, num_seeds)
+
+    def _explore(self, fn, what, cap, *args) -> list:
         n = ctypes.c_uint32()
         want = 1024 if cap is None else cap
         while True:
             arr = (Outcome * max(want, 1))()
-            _check(lib().dash_explore(self.h, src, first_seed, num_seeds, arr, want, ctypes.byref(n)),
-                   "dash_explore", self.h)
+            _check(fn(self.h, *args, arr, want, ctypes.byref(n)), what, self.h)
             if cap is not None or n.value <= want:
                 break
             want = n.value  # more outcomes than the first guess held: once more, with room for all
