@@ -418,6 +418,18 @@ def test_boundary(dash):
         assert digests(eng) == by_micro
         eng.set_micro_seeds(seeds, [1, 1, 1, 1])
         assert digests(eng) == by_micro
+        # dash_set_system_seeds takes a handle on micro seeds, whether or not a micro-step table was
+        # set before them; its NULL rebuilds the handle seed's table, which that table overwrote
+        eng.set_micro_schedule(one)
+        eng.set_micro_seeds(seeds)
+        eng.set_system_seeds(None)
+        assert digests(eng) == by_handle
+        eng.set_micro_schedule(one)
+        eng.set_micro_seeds(seeds)
+        eng.set_system_seeds(seeds)
+        assert digests(eng) == by_seeds
+        eng.set_system_seeds(None)
+        assert digests(eng) == by_handle
 
 
 # ---------------------------------------------------------------- 7. CLI

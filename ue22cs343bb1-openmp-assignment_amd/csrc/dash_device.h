@@ -29,6 +29,13 @@ enum : uint32_t {
     STAT_WORDS = 32
 };
 
+// event-log words (sim_kernel's EVLOG block writes them; dash_read_events and
+// dash_read_micro_acts decode them): one per node and round, 0 = nothing happened
+constexpr uint32_t EV_EVENT = 0x01000000u;       // bit 24: the node handled a message or issued an instruction
+constexpr uint32_t EV_INSTR = 0x80000000u;       // bit 31, with EV_EVENT: an instruction, not a message
+constexpr uint32_t EV_MICRO_SEND = 0x02000000u;  // the whole word: a seeded micro-step schedule's delivery
+                                                 // marker in the sender's slot (no event: bit 24 is clear)
+
 struct SimArgs {
     const uint2* trace;       // [group][64 lanes][chunk] x 8 B (4 packed instructions)
     const uint32_t* lens;     // [sys * N + node]

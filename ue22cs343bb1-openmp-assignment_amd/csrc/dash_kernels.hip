@@ -514,14 +514,14 @@ void sim_kernel(const SimArgs a) {
             // one word per node and round: 0 = no event; else bit 24 set, bit 31 the kind, the
             // message word in bits 0..23 and 28..30 (dash_read_events drops 7 and 15) or the
             // instruction in bits 0..15
-            const uint32_t evx = B(mHas) ? ((m & 0x70FFFFFFu) | 0x01000000u) : B(mDo) ? (ins | 0x81000000u) : 0u;
+            const uint32_t evx = B(mHas) ? ((m & 0x70FFFFFFu) | EV_EVENT) : B(mDo) ? (ins | EV_INSTR | EV_EVENT) : 0u;
             // (named words, not an array indexed by k % 4: the fast kernel's code stays the same)
             uint32_t evw = evx;
             if constexpr (MICRO) {
                 // a seeded micro-step schedule records its deliveries too: a marker in the sender's
                 // slot, an encoding no event has (bit 24 clear; not counted, dash_read_events skips
                 // it), so the log holds the whole schedule (dash_read_micro_acts)
-                if (a.arb_len == 0u) evw = wp == 2u ? 0x02000000u : evx;
+                if (a.arb_len == 0u) evw = wp == 2u ? EV_MICRO_SEND : evx;
             }
             (k % 4u == 0u ? ev0 : k % 4u == 1u ? ev1 : k % 4u == 2u ? ev2 : ev3) = evw;
             nev += B(mHas | mDo) ? 1u : 0u;

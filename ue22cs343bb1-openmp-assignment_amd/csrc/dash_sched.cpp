@@ -1,0 +1,238 @@
+// dash_sched.cpp -- C-ABI of libdash over HIP: what the runs follow (round and micro-step
+// tables, per-system seeds), dash_broadcast_system and the outcome search over seeds.
+//
+// The handle follows one source at a time (sched_src, dash_internal.h): the call made last
+// decides. d_arb holds the handle seed's own round table until an explicit table overwrites it
+// (tab_explicit); going back to the handle's seed rebuilds it.
+#include <map>
+
+#include "dash_internal.h"
+
+// every schedule call needs a handle created with a schedule seed (it owns the round table)
+static int need_seed(dash_t* h, const char* what) {
+    return h->d_arb ? DASH_OK : fail(h, DASH_ESTATE, "%s: handle created with schedule_seed = 0", what);
+}
+
+// an explicit table of `rounds` rounds: the handle's table must span the run and hold them
+static int table_fits(dash_t* h, const char* what, uint32_t rounds) {
+    if (int rc = need_seed(h, what)) return rc;
+    if (h->arb_len < h->cfg.max_rounds)
+        return fail(h, DASH_EINVAL, "%s: the round table holds %u of max_rounds %llu rounds", what, h->arb_len,
+                    (unsigned long long)h->cfg.max_rounds);
+    if (rounds > h->arb_len) return fail(h, DASH_EINVAL, "%s: %u rounds > max_rounds", what, rounds);
+    return DASH_OK;
+}
+
+// The end of every call that changes what the runs follow: the stream's work (uploads, the
+// table kernel) is done and earlier results no longer stand. rehint: which systems overflow a
+// tier depends on their schedules, so the overflow hint of earlier runs is void too.
+static int follow_now(dash_t* h, sched_src src, bool rehint) {
+    if (rehint) HIPCHK(h, reset_hint(h));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->follow = src;
+    h->ran = false;
+    return DASH_OK;
+}
+
+// tab: the kernel's table layout (dash_kernels.hip arb_table_kernel), [round / 4][lane][round % 4]
+static int upload_table(dash_t* h, const std::vector<uint32_t>& tab, sched_src src) {
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipMemcpyAsync(h->d_arb, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    const int rc = follow_now(h, src, false);
+    if (rc == DASH_OK) h->tab_explicit = true;
+    return rc;
+}
+
+// dash_set_*_seeds(NULL, 0): back to the handle's own seed and its round table, which is
+// rebuilt if an explicit table overwrote it
+static int unset_seeds(dash_t* h, const char* what, uint64_t n, bool rehint) {
+    if (n) return fail(h, DASH_EINVAL, "%s: null seeds with n = %llu", what, (unsigned long long)n);
+    if (h->tab_explicit) {
+        HIPCHK(h, dash::launch_arb_table(h->cfg.schedule_seed, h->seg, h->d_arb, h->arb_len, h->stream));
+        h->tab_explicit = false;
+    }
+    return follow_now(h, sched_src::round_table, rehint);
+}
+
+// v[words] into the seed buffer d, allocated on first use and kept
+static int upload_seeds(dash_t* h, uint64_t*& d, const char* alloc_what, const uint64_t* v, uint64_t words,
+                        sched_src src) {
+    if (!d) {
+        const hipError_t e = buf_alloc(h, d, words);
+        if (e != hipSuccess) return hip_fail(h, e, alloc_what);
+    }
+    if (words) HIPCHK(h, hipMemcpyAsync(d, v, words * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+    return follow_now(h, src, true);
+}
+
+extern "C" {
+
+int dash_set_schedule(dash_t* h, const uint8_t* sched, uint32_t rounds) {
+    return guarded(h, "dash_set_schedule", [&]() -> int {
+        if (!h || (!sched && rounds)) return DASH_EINVAL;
+        if (int rc = table_fits(h, "dash_set_schedule", rounds)) return rc;
+        const uint32_t N = h->cfg.num_procs, P = h->seg;
+        for (uint32_t r = 0; r < rounds; r++) {
+            uint32_t used = 0;
+            for (uint32_t t = 0; t < N; t++) {
+                const uint8_t v = sched[(uint64_t)r * N + t];
+                if (v == DASH_SIT_OUT) continue;
+                if (v >= P || (used >> v) & 1u)
+                    return fail(h, DASH_EINVAL, "dash_set_schedule: round %u node %u: position %u invalid or repeated",
+                                r, t, (unsigned)v);
+                used |= 1u << v;
+            }
+        }
+        // each word 0 for a node sitting out, else its primary arrival bit 2 << 4 * position
+        std::vector<uint32_t> tab(((uint64_t)h->arb_len + 4) * P, 0);
+        for (uint64_t r = 0; r < (uint64_t)h->arb_len + 4; r++)
+            for (uint32_t t = 0; t < P; t++) {
+                uint32_t w = 0;
+                if (t < N) {
+                    const uint32_t v = r < rounds ? sched[r * N + t] : t;  // later rounds: lockstep
+                    w = v == DASH_SIT_OUT ? 0u : 2u << (4u * v);
+                }
+                tab[((r >> 2) * P + t) * 4 + (r & 3)] = w;
+            }
+        return upload_table(h, tab, sched_src::round_table);
+    });
+}
+
+int dash_set_micro_schedule(dash_t* h, const uint8_t* acts, uint32_t rounds) {
+    return guarded(h, "dash_set_micro_schedule", [&]() -> int {
+        if (!h || (!acts && rounds)) return DASH_EINVAL;
+        if (int rc = table_fits(h, "dash_set_micro_schedule", rounds)) return rc;
+        const uint32_t N = h->cfg.num_procs, P = h->seg;
+        for (uint32_t r = 0; r < rounds; r++) {
+            uint32_t acting = 0;
+            for (uint32_t t = 0; t < N; t++) {
+                const uint8_t v = acts[(uint64_t)r * N + t];
+                if (v == DASH_SIT_OUT) continue;
+                if (v != DASH_MICRO_STEP && v != DASH_MICRO_SEND)
+                    return fail(h, DASH_EINVAL, "dash_set_micro_schedule: round %u node %u: action %u invalid", r, t,
+                                (unsigned)v);
+                ++acting;
+            }
+            if (acting > 1) return fail(h, DASH_EINVAL, "dash_set_micro_schedule: round %u: %u nodes act", r, acting);
+        }
+        // table words (dash_kernels.hip MODE 4): 0 = sits out, 1 = steps, 2 = sends one held
+        // message; every node sits out past the schedule
+        std::vector<uint32_t> tab(((uint64_t)h->arb_len + 4) * P, 0);
+        for (uint64_t r = 0; r < rounds; r++)
+            for (uint32_t t = 0; t < N; t++) {
+                const uint8_t v = acts[r * N + t];
+                tab[((r >> 2) * P + t) * 4 + (r & 3)] = v == DASH_SIT_OUT ? 0u : v == DASH_MICRO_STEP ? 1u : 2u;
+            }
+        return upload_table(h, tab, sched_src::micro_table);
+    });
+}
+
+int dash_set_system_seeds(dash_t* h, const uint64_t* seeds, uint64_t n) {
+    return guarded(h, "dash_set_system_seeds", [&]() -> int {
+        if (!h) return DASH_EINVAL;
+        if (int rc = need_seed(h, "dash_set_system_seeds")) return rc;
+        if (h->follow == sched_src::micro_table)
+            return fail(h, DASH_ESTATE, "dash_set_system_seeds: the handle follows a micro-step schedule");
+        HIPCHK(h, hipSetDevice(h->cfg.device));
+        // leaving the seeds voids the hint they made; a round table's own hint still stands
+        if (!seeds) return unset_seeds(h, "dash_set_system_seeds", n, h->follow == sched_src::system_seeds);
+        if (n != h->cfg.num_systems)
+            return fail(h, DASH_EINVAL, "dash_set_system_seeds: %llu seeds for %llu systems", (unsigned long long)n,
+                        (unsigned long long)h->cfg.num_systems);
+        return upload_seeds(h, h->d_seeds, "hipMalloc(seeds)", seeds, n, sched_src::system_seeds);
+    });
+}
+
+int dash_set_micro_seeds(dash_t* h, const uint64_t* seeds, const uint64_t* weights, uint64_t n) {
+    return guarded(h, "dash_set_micro_seeds", [&]() -> int {
+        if (!h) return DASH_EINVAL;
+        if (int rc = need_seed(h, "dash_set_micro_seeds")) return rc;
+        HIPCHK(h, hipSetDevice(h->cfg.device));
+        if (!seeds) return unset_seeds(h, "dash_set_micro_seeds", n, true);
+        if (n != h->cfg.num_systems)
+            return fail(h, DASH_EINVAL, "dash_set_micro_seeds: %llu seeds for %llu systems", (unsigned long long)n,
+                        (unsigned long long)h->cfg.num_systems);
+        std::vector<uint64_t> pairs(2 * n);
+        for (uint64_t k = 0; k < n; k++) {
+            const uint64_t w = weights ? weights[k] : DASH_MICRO_UNIFORM;
+            if (w & 0xE0E0E0E0E0E0E0E0ull)
+                return fail(h, DASH_EINVAL, "dash_set_micro_seeds: system %llu: a weight above 31", (unsigned long long)k);
+            pairs[2 * k] = seeds[k];
+            pairs[2 * k + 1] = w;
+        }
+        // (micro-step runs take no tiers: the hint of earlier runs is void)
+        return upload_seeds(h, h->d_mseeds, "hipMalloc(micro seeds)", pairs.data(), pairs.size(), sched_src::micro_seeds);
+    });
+}
+
+int dash_broadcast_system(dash_t* h, uint64_t src) {
+    if (!h) return DASH_EINVAL;
+    if (!h->loaded) return fail(h, DASH_ESTATE, "dash_broadcast_system: no traces loaded");
+    if (src >= h->cfg.num_systems) return fail(h, DASH_EINVAL, "dash_broadcast_system: system out of range");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, dash::launch_broadcast(h->d_trace, h->d_lens, h->cfg.num_systems, src, (uint64_t)h->seg * h->nchunks,
+                                     h->cfg.num_procs, h->stream));
+    HIPCHK(h, reset_hint(h));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->ran = false;
+    return DASH_OK;
+}
+
+// dash_explore and dash_explore_micro: broadcast, passes of num_systems seeds, the merge of their
+// outcomes. weights == nullptr: seeded round schedules (dash_set_system_seeds); else seeded
+// micro-step schedules under that one weight vector (dash_set_micro_seeds).
+static int explore_impl(dash_t* h, const char* what, uint64_t src, uint64_t first_seed, uint64_t num_seeds,
+                        const uint64_t* weights, dash_outcome* out, uint32_t cap, uint32_t* n) {
+    return guarded(h, what, [&]() -> int {
+        if (!h || !n || (!out && cap)) return DASH_EINVAL;
+        *n = 0;
+        const uint64_t nsys = h->cfg.num_systems;
+        if (int rc = need_seed(h, what)) return rc;
+        if (!weights && h->follow == sched_src::micro_table)
+            return fail(h, DASH_ESTATE, "%s: the handle follows a micro-step schedule", what);
+        if (num_seeds && !nsys) return fail(h, DASH_EINVAL, "%s: the handle has no systems", what);
+        int rc = dash_broadcast_system(h, src);
+        if (rc != DASH_OK) return rc;
+        std::vector<uint64_t> seeds(nsys), dig(nsys), wts(weights ? nsys : 0, weights ? *weights : 0);
+        std::vector<uint32_t> rnd(nsys), err(nsys);
+        std::vector<dash_outcome> found;
+        std::map<std::pair<uint64_t, uint32_t>, size_t> index;  // (digest, errors) -> found[]
+        for (uint64_t base = 0; base < num_seeds; base += nsys) {
+            const uint64_t fresh = std::min<uint64_t>(nsys, num_seeds - base);
+            // the last pass pads with repeats of its own seeds, which are not counted
+            for (uint64_t i = 0; i < nsys; i++) seeds[i] = first_seed + base + i % fresh;
+            rc = weights ? dash_set_micro_seeds(h, seeds.data(), wts.data(), nsys)
+                         : dash_set_system_seeds(h, seeds.data(), nsys);
+            if (rc != DASH_OK) return rc;
+            if ((rc = dash_run(h, nullptr)) != DASH_OK) return rc;
+            if ((rc = dash_read_results(h, 0, nsys, dig.data(), rnd.data(), err.data())) != DASH_OK) return rc;
+            for (uint64_t i = 0; i < fresh; i++) {
+                const auto it = index.emplace(std::make_pair(dig[i], err[i]), found.size());
+                if (it.second) found.push_back(dash_outcome{dig[i], 0, seeds[i], rnd[i], err[i]});
+                dash_outcome& o = found[it.first->second];
+                o.count++;
+                if (seeds[i] < o.seed) {  // only when first_seed + i wrapped past 2^64
+                    o.seed = seeds[i];
+                    o.rounds = rnd[i];
+                }
+            }
+        }
+        std::sort(found.begin(), found.end(), [](const dash_outcome& a, const dash_outcome& b) { return a.seed < b.seed; });
+        *n = (uint32_t)std::min<size_t>(found.size(), 0xFFFFFFFFu);
+        for (size_t k = 0; k < found.size() && k < cap; k++) out[k] = found[k];
+        return DASH_OK;
+    });
+}
+
+int dash_explore(dash_t* h, uint64_t src, uint64_t first_seed, uint64_t num_seeds, dash_outcome* out, uint32_t cap,
+                 uint32_t* n) {
+    return explore_impl(h, "dash_explore", src, first_seed, num_seeds, nullptr, out, cap, n);
+}
+
+int dash_explore_micro(dash_t* h, uint64_t src, uint64_t first_seed, uint64_t num_seeds, uint64_t weights,
+                       dash_outcome* out, uint32_t cap, uint32_t* n) {
+    if (h && (weights & 0xE0E0E0E0E0E0E0E0ull)) return fail(h, DASH_EINVAL, "dash_explore_micro: a weight above 31");
+    return explore_impl(h, "dash_explore_micro", src, first_seed, num_seeds, &weights, out, cap, n);
+}
+
+}  // extern "C"

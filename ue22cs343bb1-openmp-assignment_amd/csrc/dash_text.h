@@ -1,5 +1,5 @@
 /* dash_text.h -- the one-file reader shared by dash_read_dirs_text (dash_text.c) and the
-   reader threads of dash_load_dirs_device (dash_api.cpp). Internal: not part of dash.h. */
+   reader threads of dash_load_dirs_device (dash_load.cpp). Internal: not part of dash.h. */
 #ifndef DASH_TEXT_H
 #define DASH_TEXT_H
 
