@@ -41,10 +41,15 @@ enum {
 
 /* Mutation testing of the reference pin (tests/test_reference_cross_node.py): ORC_MUTANT = k
    builds oracle/_mut/libdash_oracle_m<k>.so with one plausible misreading of a cross-node
-   handler (listed in tests/ref_pin.py MUTANTS). The shipped checker is ORC_MUTANT 0. */
+   handler (listed in tests/ref_pin.py MUTANTS). The shipped checker is ORC_MUTANT 0.
+   14 and up are not misreadings of the reference but slips of single terms of the GPU kernel's
+   mask algebra (csrc/dash_kernels.hip, the 13-way dispatch), restated at this level; each names
+   the kernel expression it mirrors. The adequacy corpus (tests/adequacy.py) must tell every
+   mutant apart from the checker. */
 #ifndef ORC_MUTANT
 #define ORC_MUTANT 0
 #endif
+#define MUT(k) (ORC_MUTANT == (k))
 
 #define MAX_RING 256
 #define MAX_OUT (ORC_MAX_PROCS + 4)
@@ -95,6 +100,7 @@ static void send_message(onode *nd, int receiver, omsg m) {
 static void handle_cache_replacement(onode *nd, int sender, oline old) {
     int home = (old.address >> 4) & 0x0F;
     omsg m = {0};
+    if (MUT(23) && old.state == EXCLUSIVE) old.state = MODIFIED; /* kernel: evb */
     switch (old.state) {
     case EXCLUSIVE:
     case SHARED:
@@ -132,6 +138,8 @@ static void handle_message(osys *sy, int tid, omsg msg) {
         sy->log_len += (uint64_t)snprintf(sy->log + sy->log_len, sy->log_cap - sy->log_len,
                                           "Processor %d msg from: %d, type: %d, address: 0x%02X\n", tid,
                                           msg.sender, msg.type, msg.address);
+    /* kernel: the UPGRADE rows of the reply tables (tatab, vstab) at ds != S */
+    if (MUT(26) && msg.type == UPGRADE && nd->dirState[memBlockAddr] != S) msg.type = WRITE_REQUEST;
     switch (msg.type) {
     case READ_REQUEST: /* ref :191-237 */
         if (nd->dirState[memBlockAddr] == EM) {
@@ -162,7 +170,7 @@ static void handle_message(osys *sy, int tid, omsg msg) {
         break;
 
     case REPLY_RD: /* ref :239-255 */
-        if (L->address != msg.address && L->state != INVALID)
+        if ((MUT(22) || L->address != msg.address) && L->state != INVALID) /* kernel: ~mSame in mEv */
             handle_cache_replacement(nd, tid, *L);
         L->address = msg.address;
         L->value = msg.value;
@@ -177,7 +185,7 @@ static void handle_message(osys *sy, int tid, omsg msg) {
         r.value = L->value;
         r.secondReceiver = msg.secondReceiver;
         send_message(nd, procNodeAddr, r);
-        if (procNodeAddr != msg.secondReceiver)
+        if (MUT(21) || procNodeAddr != msg.secondReceiver) /* kernel: H != msr in mVB */
             send_message(nd, msg.secondReceiver, r);
         if (ORC_MUTANT != 1 || L->address == msg.address)
             L->state = SHARED;
@@ -185,12 +193,14 @@ static void handle_message(osys *sy, int tid, omsg msg) {
 
     case FLUSH: /* ref :288-323 */
         if (tid == procNodeAddr) {
-            nd->dirState[memBlockAddr] = S;
+            if (!MUT(20) || nd->dirState[memBlockAddr] == EM) /* kernel: mFLUSH & mtH in nds */
+                nd->dirState[memBlockAddr] = S;
+            if (MUT(18)) nd->bitVector[memBlockAddr] = 0; /* kernel: hbv */
             nd->bitVector[memBlockAddr] |= (uint8_t)(1u << msg.secondReceiver);
             nd->memory[memBlockAddr] = msg.value;
         }
         if (tid == msg.secondReceiver) {
-            if (L->address != msg.address && L->state != INVALID)
+            if ((MUT(22) || L->address != msg.address) && L->state != INVALID)
                 handle_cache_replacement(nd, tid, *L);
             L->address = msg.address;
             L->value = msg.value;
@@ -213,6 +223,9 @@ static void handle_message(osys *sy, int tid, omsg msg) {
     }
 
     case REPLY_ID: /* ref :351-387; fills with the last issued instr.value */
+        /* kernel: arrival bits 0 (INV) and 1 (primary) of a sender */
+        if (MUT(27) && L->address != msg.address && L->state != INVALID)
+            handle_cache_replacement(nd, tid, *L);
         for (int i = 0; i < sy->N; i++) {
             if (msg.bitVector & (1u << i)) {
                 omsg inv = {0};
@@ -222,7 +235,7 @@ static void handle_message(osys *sy, int tid, omsg msg) {
                 send_message(nd, i, inv);
             }
         }
-        if (L->address != msg.address && L->state != INVALID)
+        if (!MUT(27) && (MUT(22) || L->address != msg.address) && L->state != INVALID)
             handle_cache_replacement(nd, tid, *L);
         L->address = msg.address;
         L->value = nd->instr_value;
@@ -231,7 +244,8 @@ static void handle_message(osys *sy, int tid, omsg msg) {
         break;
 
     case INV: /* ref :389-399; state not checked */
-        if (L->address == msg.address && (ORC_MUTANT != 11 || L->state == SHARED))
+        /* kernel: mSame in mToI */
+        if ((MUT(32) || L->address == msg.address) && (ORC_MUTANT != 11 || L->state == SHARED))
             L->state = INVALID;
         break;
 
@@ -283,22 +297,25 @@ static void handle_message(osys *sy, int tid, omsg msg) {
         send_message(nd, procNodeAddr, r);
         if (ORC_MUTANT != 4 || procNodeAddr != msg.secondReceiver)
             send_message(nd, msg.secondReceiver, r);
-        L->state = INVALID;
+        if (!MUT(29) || L->address == msg.address) /* kernel: mWBINV in mToI */
+            L->state = INVALID;
         break;
 
     case FLUSH_INVACK: /* ref :505-536 */
         if (tid == procNodeAddr) {
-            nd->bitVector[memBlockAddr] = (uint8_t)(1u << msg.secondReceiver);
-            nd->memory[memBlockAddr] = msg.value;
+            if (!MUT(17)) nd->bitVector[memBlockAddr] = 0; /* kernel: hbv */
+            nd->bitVector[memBlockAddr] |= (uint8_t)(1u << msg.secondReceiver);
+            if (!MUT(19)) nd->memory[memBlockAddr] = msg.value; /* kernel: mHomeH in ebase */
         }
         if (tid == msg.secondReceiver) {
-            if (L->address != msg.address && L->state != INVALID)
+            if ((MUT(22) || L->address != msg.address) && L->state != INVALID)
                 handle_cache_replacement(nd, tid, *L);
             L->address = msg.address;
             L->value = ORC_MUTANT == 5 ? msg.value : nd->instr_value;
             L->state = MODIFIED;
         }
-        nd->waiting = 0;
+        if (!MUT(28) || tid == msg.secondReceiver) /* kernel: mFIA in wmask */
+            nd->waiting = 0;
         break;
 
     case EVICT_SHARED: /* ref :538-590 */
@@ -309,11 +326,13 @@ static void handle_message(osys *sy, int tid, omsg msg) {
             nd->bitVector[memBlockAddr] &= (uint8_t)~(1u << msg.sender);
             int numSharers = __builtin_popcount(nd->bitVector[memBlockAddr]);
             if (numSharers == 0) {
-                nd->dirState[memBlockAddr] = U;
+                if (!MUT(15)) nd->dirState[memBlockAddr] = U; /* kernel: es_pop == 0 in nds */
             } else if (numSharers == 1) {
-                nd->dirState[memBlockAddr] = EM;
+                if (!MUT(16)) nd->dirState[memBlockAddr] = EM; /* kernel: mEsOne in nds */
                 int newOwner = ctz8(nd->bitVector[memBlockAddr]);
-                if (newOwner != procNodeAddr) {
+                if (MUT(14) && newOwner != procNodeAddr) {
+                    /* kernel: mEsOne & ~mOwnHome in mVA -- no notice to the last sharer */
+                } else if (newOwner != procNodeAddr) {
                     r.type = EVICT_SHARED;
                     r.sender = (uint8_t)tid;
                     r.address = msg.address;
@@ -328,7 +347,7 @@ static void handle_message(osys *sy, int tid, omsg msg) {
 
     case EVICT_MODIFIED: /* ref :592-617 */
         if (ORC_MUTANT == 12 && nd->bitVector[memBlockAddr] != (uint8_t)(1u << msg.sender)) break;
-        nd->memory[memBlockAddr] = msg.value;
+        if (!MUT(31)) nd->memory[memBlockAddr] = msg.value; /* kernel: mEMOD in ebase */
         nd->bitVector[memBlockAddr] = 0;
         nd->dirState[memBlockAddr] = U;
         break;
@@ -346,7 +365,7 @@ static void issue_instruction(osys *sy, int tid) {
     uint8_t value = type == 'W' ? (uint8_t)(w & 0xFF) : 0;
     nd->instr_type = type;
     nd->instr_address = address;
-    nd->instr_value = value;
+    if (!MUT(24) || type == 'W') nd->instr_value = value; /* kernel: last_val */
     sy->res->instructions++;
 
     if (sy->log && sy->log_len + 64 < sy->log_cap) /* DEBUG_INSTR (ref :650-651) */
@@ -358,7 +377,7 @@ static void issue_instruction(osys *sy, int tid) {
     uint8_t memBlockAddr = address & 0x0F;
     uint8_t cacheIndex = memBlockAddr % sy->CS;
     oline *L = &nd->cache[cacheIndex];
-    int hit = L->address == address ? (L->state == INVALID ? 0 : 1) : 0; /* ref :662-664 */
+    int hit = L->address == address ? (L->state == INVALID && !MUT(30) ? 0 : 1) : 0; /* ref :662-664; kernel: mHit */
     omsg m = {0};
     if (type == 'R') {
         if (!hit) {
@@ -374,7 +393,7 @@ static void issue_instruction(osys *sy, int tid) {
                 L->value = value;
                 if (ORC_MUTANT != 13 || L->state == MODIFIED) L->state = MODIFIED;
             } else {
-                m.type = UPGRADE;
+                m.type = MUT(25) ? WRITE_REQUEST : UPGRADE; /* kernel: the tA patch of a WR hit */
                 m.sender = (uint8_t)tid;
                 m.address = address;
                 m.value = value;
@@ -575,6 +594,38 @@ int orc_run_system(const orc_cfg *cfg, const uint16_t *trace, uint64_t stride,
     out->digest = d;
     free(sy);
     return 0;
+}
+
+void orc_run_many(const orc_cfg *cfg, const uint16_t *traces, uint64_t sys_stride, uint64_t stride,
+                  const uint32_t *lens, const uint64_t *seeds, uint64_t count, int threads,
+                  uint64_t *digests, uint32_t *rounds, uint32_t *errors, uint32_t *hist,
+                  uint32_t *max_depth) {
+    const int nthr = threads > 0 ? threads : 1;
+    (void)nthr;
+#ifdef _OPENMP
+#pragma omp parallel num_threads(nthr)
+#endif
+    {
+        orc_result *res = (orc_result *)malloc(sizeof(orc_result));
+#ifdef _OPENMP
+#pragma omp for schedule(dynamic, 16)
+#endif
+        for (int64_t k = 0; k < (int64_t)count; k++) {
+            orc_cfg c = *cfg;
+            if (seeds) c.arb_seed = seeds[k];
+            if (orc_run_system(&c, traces + (uint64_t)k * sys_stride, stride,
+                               lens + (uint64_t)k * (uint64_t)cfg->num_procs, res, NULL, 0) != 0) {
+                memset(res, 0, sizeof *res);
+                res->errors = 0xFFFFFFFFu; /* rejected configuration or trace */
+            }
+            digests[k] = res->digest;
+            rounds[k] = (uint32_t)res->rounds;
+            errors[k] = res->errors;
+            for (int j = 0; j < ORC_NUM_TXN; j++) hist[k * ORC_NUM_TXN + j] = (uint32_t)res->hist[j];
+            if (max_depth) max_depth[k] = res->max_depth;
+        }
+        free(res);
+    }
 }
 
 /* ---- synthetic traces (spec shared with the device generator) ---- */

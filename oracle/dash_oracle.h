@@ -108,6 +108,16 @@ typedef struct orc_result {
 int orc_run_system(const orc_cfg *cfg, const uint16_t *trace, uint64_t stride,
                    const uint32_t *lens, orc_result *out, char *log, uint64_t log_cap);
 
+/* orc_run_system over `count` systems (system k's rows at traces + k * sys_stride, its lengths at
+   lens + k * num_procs, its arb_seed seeds[k] unless seeds is NULL), `threads` OpenMP threads:
+   per system the digest, rounds, error bits (all ones: rejected), hist[ORC_NUM_TXN] and, unless
+   NULL, max_depth. For the adequacy search (tests/adequacy.py), which runs every candidate under
+   every mutant build. */
+void orc_run_many(const orc_cfg *cfg, const uint16_t *traces, uint64_t sys_stride, uint64_t stride,
+                  const uint32_t *lens, const uint64_t *seeds, uint64_t count, int threads,
+                  uint64_t *digests, uint32_t *rounds, uint32_t *errors, uint32_t *hist,
+                  uint32_t *max_depth);
+
 /* Synthetic generator: identical spec to the device generator. */
 typedef struct orc_gen {
     uint64_t seed;

@@ -115,7 +115,15 @@ __device__ __forceinline__ uint32_t arb_lane(uint64_t seed, uint32_t round, uint
     const uint32_t A = ((uint32_t)key & (P - 1)) | 1u, Bc = (uint32_t)(key >> 8) & (P - 1);
     const bool lock = seed == 0;
     const uint32_t pos = lock ? t : (t * A + Bc) & (P - 1);
-    return (!lock && ((uint32_t)(skey >> (8 * t)) & 3u) == 0) ? 0u : 2u << (4u * pos);
+    // Both hashes run on every lane and the word is built from their bits arithmetically, behind
+    // a barrier: written as `(!lock && stall) ? 0 : 2 << 4 * pos` the compiler put the hashes
+    // under a branch on the seed, and at P = 1 (pos is constant) the fourth word of a trip lost
+    // its non-zero value there, so every round 4k + 3 of a one-node system sat out
+    // (tests/test_gpu_adequacy.py, N = 1 under per-system seeds).
+    uint32_t sbits = (uint32_t)(skey >> (8 * t)) & 3u;
+    asm volatile("" : "+v"(sbits));
+    const uint32_t go = (lock ? 1u : 0u) | (sbits != 0 ? 1u : 0u);  // 0: the node sits the round out
+    return (go + go) << (4u * pos);
 }
 
 // The seeded micro-step schedule's pick (include/dash.h states the rule; host twin dash_micro_pick):
