@@ -299,6 +299,76 @@ int dash_read_hist(dash_t *h, uint64_t sys, uint32_t *hist /* [DASH_NUM_TXN] */)
    trace_events rounds rounded up to a multiple of 4 (a node logs at most one event per round);
    DASH_ETRUNC if events fell past them (counted in *n, not kept). */
 int dash_read_events(dash_t *h, uint64_t sys, dash_event *out, uint32_t cap, uint32_t *n);
+
+/* ---- per-node cache and coherence metrics, reduced on the device from the event log
+   (csrc/dash_metrics.hip) ----
+   Every metric is a pure function of one system's event log over its kept rounds [0, K),
+   K = min(rounds[sys], the log's rounds). A "word" is node t's log word of round r; an "event" is a
+   word of a round in which t handled a message or issued an instruction (what dash_read_events
+   returns); an event is an instruction (DASH_EV_INSTR) or a popped message (DASH_EV_MSG) with the
+   type, sender and address fields documented for dash_event.word. The "completing types" are
+   REPLY_RD, REPLY_WR, REPLY_ID, FLUSH and FLUSH_INVACK: exactly the pops that clear
+   waitingForReply in the reference.
+
+   reads, writes          instruction events of node t, by bit 15 of the instruction (set = WR)
+   read_misses, write_misses, upgrades
+                          READ_REQUEST / WRITE_REQUEST / UPGRADE message events at any node whose
+                          sender is t. Requests are only ever popped at the home, so these are the
+                          requests of t that were serviced
+   msgs                   message events popped by t
+   home_requests          READ_REQUEST + WRITE_REQUEST + UPGRADE popped by t: its directory load
+   invalidations          INV popped by t
+   interventions          WRITEBACK_INV + WRITEBACK_INT popped by t
+   evict_shared, evict_modified
+                          EVICT_SHARED / EVICT_MODIFIED events with sender t that are popped at node
+                          address >> 4 (the home). This leaves out the home's forwarded EVICT_SHARED
+                          to a new owner, which is popped elsewhere
+   waits, wait_rounds, wait_max
+                          for each instruction event of t at round r0, take t's next event of a
+                          completing type, at round r1. If it comes before t's next instruction
+                          event, the span r1 - r0 is counted: waits is the count, wait_rounds the
+                          sum and wait_max the maximum of these spans. Spans are disjoint, so the
+                          sum fits 32 bits. A span still open at round K is not counted
+   deliveries             words equal to the delivery marker of a seeded micro-step schedule
+                          (non-zero only under dash_set_micro_seeds)
+   idle_rounds            K - (reads + writes + msgs) - deliveries
+
+   These are the reference's behaviour, not an approximation of ours: hits are reads - read_misses
+   (likewise for writes) for systems without DASH_ERR_OVERFLOW / _STUCK / _ROUNDCAP and with an
+   untruncated log. The reference clears waitingForReply on any completing pop, so a stray FLUSH can
+   release a waiting home early: a wait span is "issue to the pop that cleared waitingForReply", not
+   "issue to the matching reply". */
+typedef struct dash_node_metrics {
+    uint32_t reads, writes;
+    uint32_t read_misses, write_misses, upgrades;
+    uint32_t msgs, home_requests, invalidations, interventions;
+    uint32_t evict_shared, evict_modified;
+    uint32_t waits, wait_rounds, wait_max;
+    uint32_t deliveries, idle_rounds;
+} dash_node_metrics; /* 16 x uint32_t: 64 B per node */
+/* The 16 fields summed over every node of every system (wait_max: the maximum), the systems of the
+   batch, and those whose log was shorter than their run. */
+typedef struct dash_metrics_totals {
+    uint64_t reads, writes;
+    uint64_t read_misses, write_misses, upgrades;
+    uint64_t msgs, home_requests, invalidations, interventions;
+    uint64_t evict_shared, evict_modified;
+    uint64_t waits, wait_rounds, wait_max;
+    uint64_t deliveries, idle_rounds;
+    uint64_t systems, truncated_systems;
+} dash_metrics_totals;
+/* One pass of the device over the whole batch's event log of the last dash_run (any schedule; after
+   dash_explore*, the last pass): a dash_node_metrics record per node stays on the device until the
+   next dash_run, and the totals (optional) are on the host at return. DASH_ESTATE before a
+   completed dash_run and on a handle created with trace_events == 0. A log shorter than a system's
+   run is no error: that system's metrics cover rounds [0, the log's rounds), its `truncated` byte
+   is set and it counts in truncated_systems. */
+int dash_compute_metrics(dash_t *h, dash_metrics_totals *totals);
+/* Records of systems [first, first + count): out[(k - first) * num_procs + t], and (optional)
+   truncated[k - first] = 1 when rounds[k] > the log's rounds. DASH_ESTATE when no
+   dash_compute_metrics followed the last dash_run; DASH_EINVAL for a range outside the batch. */
+int dash_read_metrics(dash_t *h, uint64_t first, uint64_t count, dash_node_metrics *out,
+                      uint8_t *truncated);
 /* HIP stream the engine launches on (hipStream_t as void*) */
 void *dash_stream(dash_t *h);
 

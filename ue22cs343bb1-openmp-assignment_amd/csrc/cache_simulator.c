@@ -26,6 +26,13 @@
  *   --write-rounds FILE  after the run, write the schedule it followed (--schedule SEED, or
  *       lockstep) for the rounds it took as the plain rows --rounds reads, so that
  *       `--rounds FILE` writes the same dumps and the schedule can be read, edited and kept
+ *   --metrics         per-node cache and coherence metrics, reduced on the GPU from the run's event
+ *       log (dash_compute_metrics; the log is sized to the run): after the dumps are written, one
+ *       stdout line per node, "metrics node=<t> instructions= reads= writes= read_misses=
+ *       write_misses= upgrades= invalidations= interventions= evictions= evict_shared=
+ *       evict_modified= home_requests= waits= wait_mean= wait_max= idle_rounds=" (wait_mean and
+ *       wait_max in rounds; include/dash.h defines each count). Goes with --schedule, --rounds,
+ *       --micro and --micro-seed; in the bulk modes it prints one "metrics total ..." line
  *   --explore K       which outcomes can this directory reach? Runs K seeded legal schedules,
  *       seeds S0 .. S0 + K - 1 (S0 = --schedule, default 0 = lockstep first), in one GPU batch
  *       per 65,536 (dash_explore) and prints one line per distinct final state, "digest(hex)
@@ -201,12 +208,43 @@ static int write_micro(dash_t *h, const char *path, unsigned n) {
     return rc;
 }
 
+/* --metrics: the records of `count` systems' nodes, one line per node (count 1), or the totals */
+static int print_metrics(dash_t *h, uint64_t count, unsigned n) {
+    dash_metrics_totals tot;
+    int rc = dash_compute_metrics(h, &tot);
+    if (rc != DASH_OK) return rc;
+    if (count != 1) {
+        printf("metrics total systems=%llu truncated_systems=%llu", (unsigned long long)tot.systems,
+               (unsigned long long)tot.truncated_systems);
+        static const char *names[16] = {"reads", "writes", "read_misses", "write_misses", "upgrades", "msgs",
+                                        "home_requests", "invalidations", "interventions", "evict_shared",
+                                        "evict_modified", "waits", "wait_rounds", "wait_max", "deliveries",
+                                        "idle_rounds"};
+        uint64_t v[16]; /* the 16 fields lead the struct, in dash_node_metrics' order */
+        memcpy(v, &tot, sizeof v);
+        for (int k = 0; k < 16; k++) printf(" %s=%llu", names[k], (unsigned long long)v[k]);
+        printf(" wait_mean=%.2f\n", tot.waits ? (double)tot.wait_rounds / (double)tot.waits : 0.0);
+        return DASH_OK;
+    }
+    dash_node_metrics m[DASH_MAX_PROCS];
+    rc = dash_read_metrics(h, 0, 1, m, NULL);
+    for (unsigned t = 0; rc == DASH_OK && t < n; t++)
+        printf("metrics node=%u instructions=%u reads=%u writes=%u read_misses=%u write_misses=%u upgrades=%u "
+               "invalidations=%u interventions=%u evictions=%u evict_shared=%u evict_modified=%u home_requests=%u "
+               "waits=%u wait_mean=%.2f wait_max=%u idle_rounds=%u\n",
+               t, m[t].reads + m[t].writes, m[t].reads, m[t].writes, m[t].read_misses, m[t].write_misses,
+               m[t].upgrades, m[t].invalidations, m[t].interventions, m[t].evict_shared + m[t].evict_modified,
+               m[t].evict_shared, m[t].evict_modified, m[t].home_requests, m[t].waits,
+               m[t].waits ? (double)m[t].wait_rounds / (double)m[t].waits : 0.0, m[t].wait_max, m[t].idle_rounds);
+    return rc;
+}
+
 /* dash_simulate_dir plus a schedule (seed, explicit rounds, micro-steps, or a micro seed with its
    weights) and the event log of the one system */
 static int simulate_traced(const char *dir, unsigned n, unsigned cs, unsigned m, const char *out, int dev,
                            int dbg_instr, int dbg_msg, unsigned long long sched, const uint8_t *rounds,
                            long nrounds, int micro, const uint64_t *mseed, uint64_t weights,
-                           const char *write_micro_file, dash_stats *st) {
+                           const char *write_micro_file, int metrics, dash_stats *st) {
     dash_cfg cfg = {0};
     cfg.num_procs = n;
     cfg.cache_size = cs;
@@ -218,7 +256,7 @@ static int simulate_traced(const char *dir, unsigned n, unsigned cs, unsigned m,
        up to 2^22): n x 4 B per round on the device */
     uint64_t log_rounds = 1024u + 256ull * m;
     if (log_rounds > (1u << 22)) log_rounds = 1u << 22;
-    cfg.trace_events = (dbg_instr || dbg_msg || write_micro_file) ? (uint32_t)log_rounds : 0;
+    cfg.trace_events = (dbg_instr || dbg_msg || write_micro_file || metrics) ? (uint32_t)log_rounds : 0;
     cfg.schedule_seed = (rounds || mseed) ? (sched ? sched : 1) : sched;
     dash_t *h = NULL;
     int rc = dash_create(&cfg, &h);
@@ -253,6 +291,7 @@ static int simulate_traced(const char *dir, unsigned n, unsigned cs, unsigned m,
             if (erc != DASH_OK) rc = erc;
         }
         free(ev);
+        if (rc == DASH_OK && metrics) rc = print_metrics(h, 1, n);
     }
     if (rc != DASH_OK) fprintf(stderr, "%s\n", dash_last_error(h));
     dash_destroy(h);
@@ -343,7 +382,7 @@ typedef struct {
     unsigned long long seed, sched;
     int dev, show;
     const char *out, *digests, *dump;
-    int device_ingest;
+    int device_ingest, metrics;
 } bulk_opts;
 
 static void print_stats(const dash_stats *st);
@@ -365,6 +404,11 @@ static int finish_bulk(dash_t *h, const bulk_opts *o, const dash_stats *st, uint
     if (rc != DASH_OK) fprintf(stderr, "%s\n", dash_last_error(h));
     if (o->show) print_stats(st);
     return rc;
+}
+
+/* the event log that holds every round of a finished run (st->rounds_max), for a second run of it */
+static uint32_t log_rounds_of(const dash_stats *st) {
+    return st->rounds_max ? (uint32_t)st->rounds_max : 4u;
 }
 
 static int run_batch_list(const char *list, const bulk_opts *o) {
@@ -405,6 +449,16 @@ static int run_batch_list(const char *list, const bulk_opts *o) {
     else if (h)
         fprintf(stderr, "%s\n", dash_last_error(h));
     dash_destroy(h);
+    if (rc == DASH_OK && o->metrics) {  /* once more, with an event log of the rounds the run took */
+        cfg.flags = 0;
+        cfg.trace_events = log_rounds_of(&st);
+        h = NULL;
+        if ((rc = dash_create(&cfg, &h)) == DASH_OK && (rc = dash_load_dirs(h, (const char *const *)dirs, n)) == DASH_OK &&
+            (rc = dash_run(h, NULL)) == DASH_OK)
+            rc = print_metrics(h, 0, o->n);
+        if (rc != DASH_OK) fprintf(stderr, "%s\n", h ? dash_last_error(h) : dash_last_error(NULL));
+        dash_destroy(h);
+    }
     for (uint64_t k = 0; k < n; k++) free(dirs[k]);
     free(dirs);
     return rc;
@@ -435,6 +489,16 @@ static int run_synthetic(uint64_t count, const bulk_opts *o) {
         fprintf(stderr, "%s\n", dash_last_error(h));
     }
     dash_destroy(h);
+    if (rc == DASH_OK && o->metrics) {  /* once more, with an event log of the rounds the run took */
+        cfg.flags = 0;
+        cfg.trace_events = log_rounds_of(&st);
+        h = NULL;
+        if ((rc = dash_create(&cfg, &h)) == DASH_OK && (rc = dash_generate(h, &g)) == DASH_OK &&
+            (rc = dash_run(h, NULL)) == DASH_OK)
+            rc = print_metrics(h, 0, o->n);
+        if (rc != DASH_OK) fprintf(stderr, "%s\n", h ? dash_last_error(h) : dash_last_error(NULL));
+        dash_destroy(h);
+    }
     return rc;
 }
 
@@ -444,7 +508,7 @@ int main(int argc, char *argv[]) {
     const char *out = ".", *dir = NULL, *batch = NULL, *digests = NULL, *dump = NULL, *rounds_file = NULL,
                *micro_file = NULL, *write_rounds_file = NULL, *write_micro_file = NULL, *weights_text = NULL;
     unsigned long long synth = 0, seed = 0x5EED, sched = 0, explore = 0, micro_seed = 0;
-    int explore_given = 0, explore_micro = 0, micro_seed_given = 0;
+    int explore_given = 0, explore_micro = 0, micro_seed_given = 0, metrics = 0;
     uint64_t weights = DASH_MICRO_UNIFORM;
     unsigned len = 4096, kind = DASH_GEN_UNIFORM;
     double loc = 0.5;
@@ -457,6 +521,7 @@ int main(int argc, char *argv[]) {
         else if (!strcmp(argv[i], "-s")) show = 1;
         else if (!strcmp(argv[i], "--debug-instr")) dbg_instr = 1;
         else if (!strcmp(argv[i], "--debug-msg")) dbg_msg = 1;
+        else if (!strcmp(argv[i], "--metrics")) metrics = 1;
         else if (!strcmp(argv[i], "--batch") && i + 1 < argc) batch = argv[++i];
         else if (!strcmp(argv[i], "--device-ingest")) device_ingest = 1;
         else if (!strcmp(argv[i], "--synthetic") && i + 1 < argc) synth = strtoull(argv[++i], NULL, 0);
@@ -485,13 +550,14 @@ int main(int argc, char *argv[]) {
     if (batch || synth) {
         if (synth && !n_given) n = 8; /* synthetic systems default to 8 nodes (BASELINE configs) */
         bulk_opts o = {n, cs, m, len, kind, (unsigned)(loc * 65536.0), seed, sched, dev, show, out, digests, dump,
-                       device_ingest};
+                       device_ingest, metrics};
         if (o.locality > 65536u) o.locality = 65536u;
         int rc = batch ? run_batch_list(batch, &o) : run_synthetic(synth, &o);
         return rc == DASH_OK ? EXIT_SUCCESS : EXIT_FAILURE;
     }
     if (!dir) {
         fprintf(stderr, "Usage: %s <test_directory>\n", argv[0]); /* ref :128 */
+        fprintf(stderr, "       %s <test_directory> --metrics   per-node miss, invalidation and wait metrics\n", argv[0]);
         return EXIT_FAILURE;
     }
     if (weights_text && parse_weights(weights_text, n, &weights) != 0) {
@@ -503,8 +569,9 @@ int main(int argc, char *argv[]) {
         return EXIT_FAILURE;
     }
     if (explore_given) {
-        if (rounds_file || micro_file || write_rounds_file || write_micro_file) {
-            fprintf(stderr, "cache_simulator: --explore takes no --rounds, --micro, --write-rounds or --write-micro\n");
+        if (rounds_file || micro_file || write_rounds_file || write_micro_file || metrics) {
+            fprintf(stderr, "cache_simulator: --explore takes no --rounds, --micro, --write-rounds, --write-micro "
+                            "or --metrics\n");
             return EXIT_FAILURE;
         }
         int rc = explore_dir(dir, n, cs, m, dev, explore, explore_micro ? micro_seed : sched,
@@ -547,10 +614,10 @@ int main(int argc, char *argv[]) {
     }
     dash_stats st;
     const uint64_t mseed = micro_seed;
-    int rc = (dbg_instr || dbg_msg || sched || rounds || write_rounds_file || micro_seed_given)
+    int rc = (dbg_instr || dbg_msg || sched || rounds || write_rounds_file || micro_seed_given || metrics)
                  ? simulate_traced(dir, n, cs, m, out, dev, dbg_instr, dbg_msg, sched, rounds, nrounds,
                                    micro_file != NULL, micro_seed_given ? &mseed : NULL, weights, write_micro_file,
-                                   &st)
+                                   metrics, &st)
                  : dash_simulate_dir(dir, n, cs, m, out, dev, &st);
     free(rounds);
     if (rc == DASH_OK && write_rounds_file &&

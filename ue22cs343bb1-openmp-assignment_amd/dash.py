@@ -15,6 +15,8 @@ libdash:
     Engine.explore(src, s0, k)     -> the outcomes k seeded legal schedules of one system reach
     Engine.explore_micro(src, s0, k, weights) -> the same over seeded micro-step schedules
     Engine.read_state(sys)         -> the nodes' processorNode state
+    Engine.compute_metrics()       -> per-node miss / invalidation / wait metrics, reduced on the GPU
+                                      from the event log (read_metrics returns the records)
     dump_node(state, node)         -> printProcessorState bytes (:868-902)
     simulate_dir(dir, out_dir)     -> main() end to end
 
@@ -62,7 +64,8 @@ EXPORTS = ("dash_create", "dash_destroy", "dash_last_error", "dash_load_traces",
            "dash_set_micro_schedule", "dash_parse_core_text", "dash_read_dirs_text", "dash_load_text",
            "dash_load_dirs_device", "dash_read_traces", "dash_ingest_info", "dash_set_system_seeds",
            "dash_broadcast_system", "dash_seed_schedule", "dash_explore", "dash_micro_pick",
-           "dash_set_micro_seeds", "dash_read_micro_acts", "dash_explore_micro")
+           "dash_set_micro_seeds", "dash_read_micro_acts", "dash_explore_micro", "dash_compute_metrics",
+           "dash_read_metrics")
 TEXT_TILE = 4096  # DASH_TEXT_TILE: bytes per tile of the device text parser
 SIT_OUT = 0xFF
 MICRO_STEP, MICRO_SEND = 0, 1  # dash_set_micro_schedule actions
@@ -133,6 +136,21 @@ class Outcome(ctypes.Structure):
                 ("rounds", ctypes.c_uint32), ("errors", ctypes.c_uint32)]
 
 
+# dash_node_metrics / dash_metrics_totals (include/dash.h states what each field counts)
+METRIC_FIELDS = ("reads", "writes", "read_misses", "write_misses", "upgrades", "msgs", "home_requests",
+                 "invalidations", "interventions", "evict_shared", "evict_modified", "waits", "wait_rounds",
+                 "wait_max", "deliveries", "idle_rounds")
+METRICS_DTYPE = np.dtype([(f, np.uint32) for f in METRIC_FIELDS])
+
+
+class NodeMetrics(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint32) for f in METRIC_FIELDS]
+
+
+class MetricsTotals(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint64) for f in METRIC_FIELDS + ("systems", "truncated_systems")]
+
+
 class Gen(ctypes.Structure):
     _fields_ = [("seed", ctypes.c_uint64), ("sys_base", ctypes.c_uint64), ("kind", ctypes.c_uint32),
                 ("locality", ctypes.c_uint32), ("len", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
@@ -199,6 +217,8 @@ def lib() -> ctypes.CDLL:
         "dash_set_micro_seeds": (i32, [vp, vp, vp, u64]),
         "dash_read_micro_acts": (i32, [vp, u64, vp, u32, ctypes.POINTER(u32)]),
         "dash_explore_micro": (i32, [vp, u64, u64, u64, u64, vp, u32, ctypes.POINTER(u32)]),
+        "dash_compute_metrics": (i32, [vp, ctypes.POINTER(MetricsTotals)]),
+        "dash_read_metrics": (i32, [vp, u64, u64, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -601,6 +621,29 @@ class Engine:
         arr = (Event * max(cap, 1))()
         _check(lib().dash_read_events(self.h, sys, arr, cap, ctypes.byref(n)), "dash_read_events", self.h)
         return list(arr[:min(n.value, cap)])
+
+    def compute_metrics(self) -> dict:
+        """dash_compute_metrics: one GPU pass over the batch's event log of the last run (needs
+        trace_events). Returns the totals: every METRIC_FIELDS entry summed over all nodes (wait_max:
+        the maximum), systems and truncated_systems. The per-node records stay on the device for
+        read_metrics until the next run."""
+        t = MetricsTotals()
+        _check(lib().dash_compute_metrics(self.h, ctypes.byref(t)), "dash_compute_metrics", self.h)
+        return {f: int(getattr(t, f)) for f, _ in MetricsTotals._fields_}
+
+    def read_metrics(self, first=0, count=None):
+        """dash_read_metrics: (records, truncated) of systems [first, first + count): a structured
+        array [count, num_procs] with the METRIC_FIELDS, and uint8 [count], 1 where the log was
+        shorter than the system's run (its metrics then cover the log's rounds only)."""
+        count = self.num_systems - first if count is None else count
+        rec = np.zeros((max(count, 0), self.num_procs), dtype=METRICS_DTYPE)
+        cut = np.zeros(max(count, 0), dtype=np.uint8)
+        # a non-null pointer also for an empty window, whose range is still checked
+        out = rec if rec.size else np.zeros(1, dtype=METRICS_DTYPE)
+        flags = cut if cut.size else np.zeros(1, dtype=np.uint8)
+        _check(lib().dash_read_metrics(self.h, first, count, out.ctypes.data, flags.ctypes.data),
+               "dash_read_metrics", self.h)
+        return rec, cut
 
     def stream(self) -> int:
         return int(lib().dash_stream(self.h) or 0)
