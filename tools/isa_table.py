@@ -50,7 +50,9 @@ def extract(lib):
         g.write(f.read())
     subprocess.run([f"{LLVM}/llvm-objdump", "--offloading", dst], check=True, cwd=tmp,
                    stdout=subprocess.DEVNULL)
-    co = [p for p in os.listdir(tmp) if "gfx950" in p]
+    # one code object per offload bundle (libdash.so.<k>.hipv4-...); the sim kernels' is the first
+    # (the Makefile links dash_kernels.o first), and os.listdir's order is arbitrary
+    co = sorted(p for p in os.listdir(tmp) if "gfx950" in p)
     if not co:
         sys.exit("no gfx950 code object in " + lib)
     out = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--mcpu=gfx950", os.path.join(tmp, co[0])],
