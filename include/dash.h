@@ -83,6 +83,8 @@ enum dash_txn {
                                  the first depth adapts to the previous run's overflow rate */
 #define DASH_TEST_SHORT_ARB 8u /* testing only: the seeded schedule's round table holds 8 rounds,
                                   so later rounds take the in-kernel hashing path */
+#define DASH_TEST_ONE_GROUP 16u /* testing only: dash_check_coherence walks the batch with a single
+                                   workgroup, so a small batch takes several trips of its loop */
 
 typedef struct dash_cfg {
     uint32_t num_procs;   /* NUM_PROCS (ref :6): 4 or 8 */
@@ -369,6 +371,59 @@ int dash_compute_metrics(dash_t *h, dash_metrics_totals *totals);
    dash_compute_metrics followed the last dash_run; DASH_EINVAL for a range outside the batch. */
 int dash_read_metrics(dash_t *h, uint64_t first, uint64_t count, dash_node_metrics *out,
                       uint8_t *truncated);
+
+/* ---- coherence invariants of final states (csrc/dash_coherence.hip) ----
+   An address is a = (home << 4) | block with home < num_procs and block < 16: a system has
+   num_procs * 16 addresses. Over the final state of one system, the copies of a are the cache lines
+   (t, i), t < num_procs, i < cache_size, with cache_addr == a and cache_state != INVALID. Lines are
+   found by scanning, wherever they sit: no placement is assumed, and two valid lines of one node with
+   the same address are two copies. Lines with another address (the initial 0xFF) belong to no
+   checked address. With
+     n    = the number of copies,
+     own  = the number of copies in MODIFIED or EXCLUSIVE,
+     mask = the OR of 1 << t over the copies,
+     d, bv, mem = the home's dir_state, dir_bitvector and memory at block,
+   an address has the bit set when: */
+#define DASH_COH_SWMR 1u           /* own >= 1 && n >= 2 */
+#define DASH_COH_DIR_U_HELD 2u     /* d == U && n >= 1 */
+#define DASH_COH_DIR_EM 4u         /* d == EM && !(n == 1 && own == 1) */
+#define DASH_COH_DIR_S 8u          /* d == S && (own >= 1 || n == 0) */
+#define DASH_COH_LOST_SHARER 16u   /* d != U && (mask & ~bv) != 0 */
+#define DASH_COH_STALE_SHARER 32u  /* d != U && (bv & ~mask) != 0; bits of bv at or above num_procs count */
+#define DASH_COH_STALE_VALUE 64u   /* some copy in SHARED or EXCLUSIVE has cache_value != mem */
+#define DASH_COH_VALUE_SPLIT 128u  /* two copies differ in cache_value */
+typedef struct dash_coherence {
+    uint32_t bits;       /* OR over the system's addresses */
+    uint32_t addrs;      /* addresses with any bit */
+    uint32_t first_addr; /* lowest such address; 0xFFFFFFFF when addrs == 0 */
+    uint32_t first_bits; /* that address's bits; 0 when addrs == 0 */
+} dash_coherence;
+/* Over the batch. bit_systems[k] / bit_addrs[k]: systems / addresses with bit 1 << k. Systems with
+   DASH_ERR_* bits are checked like any other (a cut run's state is what it is);
+   violating_clean_systems leaves them out. */
+typedef struct dash_coherence_totals {
+    uint64_t systems, violating_systems;
+    uint64_t violating_clean_systems;    /* bits != 0 and errors[sys] == 0 */
+    uint64_t addrs;
+    uint64_t bit_systems[8], bit_addrs[8];
+} dash_coherence_totals;
+/* One pass of the device over the whole batch's final state of the last dash_run (after
+   dash_explore*, the last pass): a dash_coherence record per system stays on the device until the
+   next dash_run, and the totals (optional) are on the host at return. DASH_ESTATE before a completed
+   dash_run and on a handle created without DASH_KEEP_STATE. */
+int dash_check_coherence(dash_t *h, dash_coherence_totals *totals);
+/* Records of systems [first, first + count). DASH_ESTATE when no dash_check_coherence followed the
+   last dash_run; DASH_EINVAL for a range outside the batch. */
+int dash_read_coherence(dash_t *h, uint64_t first, uint64_t count, dash_coherence *out);
+/* Classifies the outcomes an explore returned: an outcome's digest is a digest of the final state,
+   so its witness seed stands for it. Broadcasts system src and runs the witness seeds outs[k].seed in
+   passes of cfg.num_systems (dash_set_system_seeds; with weights != NULL, dash_set_micro_seeds under
+   the one weight vector *weights), the last pass padded with repeats; after each pass
+   dash_check_coherence gives out[k], in the order given. DASH_ESTATE, with a message naming k, when
+   witness k did not reproduce outs[k].digest and outs[k].errors. Handle requirements as the matching
+   explore, plus DASH_KEEP_STATE. Afterwards the handle holds the last pass. */
+int dash_check_outcomes(dash_t *h, uint64_t src, const dash_outcome *outs, uint32_t n,
+                        const uint64_t *weights, dash_coherence *out /* [n] */);
 /* HIP stream the engine launches on (hipStream_t as void*) */
 void *dash_stream(dash_t *h);
 
@@ -477,6 +532,12 @@ int dash_dump_node(const dash_node_state *s, uint32_t node_id, uint32_t cache_si
 int dash_dump_file(const dash_node_state *s, uint32_t node_id, uint32_t cache_size,
                    const char *path);
 uint64_t dash_digest_node(const dash_node_state *s, uint32_t node_id, uint32_t cache_size);
+/* The coherence invariants (DASH_COH_*, above) of one system whose states the caller holds, e.g.
+   parsed dumps or dash_read_state output: the library's one statement of the rules on the host.
+   addr_bits (optional, [num_procs * 16]) gets every address's bits. DASH_EINVAL outside num_procs
+   1..8 or cache_size 1..16. */
+int dash_check_states(const dash_node_state *nodes, uint32_t num_procs, uint32_t cache_size,
+                      dash_coherence *out, uint32_t *addr_bits);
 /* One event as the reference prints it: DEBUG_MSG "Processor %d msg from: %d, type: %d,
    address: 0x%02X" (ref :180-181) or DEBUG_INSTR "Processor %d: instr type=%c,
    address=0x%02X, value=%hhu" (ref :650-651), newline included. Returns bytes or < 0. */

@@ -33,6 +33,12 @@
  *       evict_modified= home_requests= waits= wait_mean= wait_max= idle_rounds=" (wait_mean and
  *       wait_max in rounds; include/dash.h defines each count). Goes with --schedule, --rounds,
  *       --micro and --micro-seed; in the bulk modes it prints one "metrics total ..." line
+ *   --coherence       the coherence invariants of the final state, checked on the GPU
+ *       (dash_check_coherence; include/dash.h defines the DASH_COH_* bits): after the dumps, one stdout
+ *       line "coherence addrs=<K> bits=0x<BB>", K = addresses that break an invariant, followed by
+ *       " first=0x<AA> first_bits=0x<BB>" (the lowest such address and its bits) when K > 0. Goes with
+ *       --schedule, --rounds, --micro and --micro-seed; with --explore / --explore-micro every outcome
+ *       line gains a sixth column, the outcome's bits in hex (dash_check_outcomes)
  *   --explore K       which outcomes can this directory reach? Runs K seeded legal schedules,
  *       seeds S0 .. S0 + K - 1 (S0 = --schedule, default 0 = lockstep first), in one GPU batch
  *       per 65,536 (dash_explore) and prints one line per distinct final state, "digest(hex)
@@ -239,12 +245,24 @@ static int print_metrics(dash_t *h, uint64_t count, unsigned n) {
     return rc;
 }
 
+/* --coherence: the one system's record as a line */
+static int print_coherence(dash_t *h) {
+    dash_coherence c;
+    int rc = dash_check_coherence(h, NULL);
+    if (rc == DASH_OK) rc = dash_read_coherence(h, 0, 1, &c);
+    if (rc != DASH_OK) return rc;
+    printf("coherence addrs=%u bits=0x%X", c.addrs, c.bits);
+    if (c.addrs) printf(" first=0x%02X first_bits=0x%X", c.first_addr, c.first_bits);
+    printf("\n");
+    return DASH_OK;
+}
+
 /* dash_simulate_dir plus a schedule (seed, explicit rounds, micro-steps, or a micro seed with its
    weights) and the event log of the one system */
 static int simulate_traced(const char *dir, unsigned n, unsigned cs, unsigned m, const char *out, int dev,
                            int dbg_instr, int dbg_msg, unsigned long long sched, const uint8_t *rounds,
                            long nrounds, int micro, const uint64_t *mseed, uint64_t weights,
-                           const char *write_micro_file, int metrics, dash_stats *st) {
+                           const char *write_micro_file, int metrics, int coherence, dash_stats *st) {
     dash_cfg cfg = {0};
     cfg.num_procs = n;
     cfg.cache_size = cs;
@@ -292,6 +310,7 @@ static int simulate_traced(const char *dir, unsigned n, unsigned cs, unsigned m,
         }
         free(ev);
         if (rc == DASH_OK && metrics) rc = print_metrics(h, 1, n);
+        if (rc == DASH_OK && coherence) rc = print_coherence(h);
     }
     if (rc != DASH_OK) fprintf(stderr, "%s\n", dash_last_error(h));
     dash_destroy(h);
@@ -322,7 +341,7 @@ static int write_rounds(const char *path, unsigned long long sched, unsigned n, 
 /* --explore K / --explore-micro K (weights != NULL): the distinct outcomes of K seeded schedules of one
    trace directory */
 static int explore_dir(const char *dir, unsigned n, unsigned cs, unsigned m, int dev, unsigned long long k,
-                       unsigned long long s0, const uint64_t *weights) {
+                       unsigned long long s0, const uint64_t *weights, int coherence) {
     char base[4096], path[4200];
     int rc = dash_resolve_dir(dir, base, sizeof base);
     if (rc != DASH_OK || n < 1 || n > DASH_MAX_PROCS) {
@@ -345,6 +364,7 @@ static int explore_dir(const char *dir, unsigned n, unsigned cs, unsigned m, int
     cfg.num_systems = nsys;
     cfg.device = dev;
     cfg.schedule_seed = 1; /* any seeded handle: every system gets a seed of its own */
+    cfg.flags = coherence ? DASH_KEEP_STATE : 0; /* the final states stay on the device for the check */
     if (!tr || !lens) rc = DASH_ENOMEM;
     for (unsigned t = 0; rc == DASH_OK && t < n; t++) {
         snprintf(path, sizeof path, "%s/core_%u.txt", base, t);
@@ -365,9 +385,18 @@ static int explore_dir(const char *dir, unsigned n, unsigned cs, unsigned m, int
                  : weights ? dash_explore_micro(h, 0, s0, k, *weights, o, cap, &total)
                            : dash_explore(h, 0, s0, k, o, cap, &total);
         }
-        for (uint32_t i = 0; rc == DASH_OK && i < total && i < cap; i++)
-            printf("%016llx %llu %llu %u %x\n", (unsigned long long)o[i].digest, (unsigned long long)o[i].count,
+        dash_coherence *c = NULL;
+        if (rc == DASH_OK && coherence) {
+            c = (dash_coherence *)malloc((total ? total : 1) * sizeof *c);
+            rc = c ? dash_check_outcomes(h, 0, o, total, weights, c) : DASH_ENOMEM;
+        }
+        for (uint32_t i = 0; rc == DASH_OK && i < total && i < cap; i++) {
+            printf("%016llx %llu %llu %u %x", (unsigned long long)o[i].digest, (unsigned long long)o[i].count,
                    (unsigned long long)o[i].seed, o[i].rounds, o[i].errors);
+            if (c) printf(" %x", c[i].bits);
+            printf("\n");
+        }
+        free(c);
         free(o);
     }
     if (rc != DASH_OK && h) fprintf(stderr, "%s\n", dash_last_error(h));
@@ -508,7 +537,7 @@ int main(int argc, char *argv[]) {
     const char *out = ".", *dir = NULL, *batch = NULL, *digests = NULL, *dump = NULL, *rounds_file = NULL,
                *micro_file = NULL, *write_rounds_file = NULL, *write_micro_file = NULL, *weights_text = NULL;
     unsigned long long synth = 0, seed = 0x5EED, sched = 0, explore = 0, micro_seed = 0;
-    int explore_given = 0, explore_micro = 0, micro_seed_given = 0, metrics = 0;
+    int explore_given = 0, explore_micro = 0, micro_seed_given = 0, metrics = 0, coherence = 0;
     uint64_t weights = DASH_MICRO_UNIFORM;
     unsigned len = 4096, kind = DASH_GEN_UNIFORM;
     double loc = 0.5;
@@ -522,6 +551,7 @@ int main(int argc, char *argv[]) {
         else if (!strcmp(argv[i], "--debug-instr")) dbg_instr = 1;
         else if (!strcmp(argv[i], "--debug-msg")) dbg_msg = 1;
         else if (!strcmp(argv[i], "--metrics")) metrics = 1;
+        else if (!strcmp(argv[i], "--coherence")) coherence = 1;
         else if (!strcmp(argv[i], "--batch") && i + 1 < argc) batch = argv[++i];
         else if (!strcmp(argv[i], "--device-ingest")) device_ingest = 1;
         else if (!strcmp(argv[i], "--synthetic") && i + 1 < argc) synth = strtoull(argv[++i], NULL, 0);
@@ -558,6 +588,7 @@ int main(int argc, char *argv[]) {
     if (!dir) {
         fprintf(stderr, "Usage: %s <test_directory>\n", argv[0]); /* ref :128 */
         fprintf(stderr, "       %s <test_directory> --metrics   per-node miss, invalidation and wait metrics\n", argv[0]);
+        fprintf(stderr, "       %s <test_directory> --coherence   coherence invariants of the final state\n", argv[0]);
         return EXIT_FAILURE;
     }
     if (weights_text && parse_weights(weights_text, n, &weights) != 0) {
@@ -575,7 +606,7 @@ int main(int argc, char *argv[]) {
             return EXIT_FAILURE;
         }
         int rc = explore_dir(dir, n, cs, m, dev, explore, explore_micro ? micro_seed : sched,
-                             explore_micro ? &weights : NULL);
+                             explore_micro ? &weights : NULL, coherence);
         if (rc != DASH_OK) {
             const char *why = dash_last_error(NULL);
             fprintf(stderr, "cache_simulator: %s (%d)\n", why[0] ? why : "failed", rc);
@@ -614,10 +645,10 @@ int main(int argc, char *argv[]) {
     }
     dash_stats st;
     const uint64_t mseed = micro_seed;
-    int rc = (dbg_instr || dbg_msg || sched || rounds || write_rounds_file || micro_seed_given || metrics)
+    int rc = (dbg_instr || dbg_msg || sched || rounds || write_rounds_file || micro_seed_given || metrics || coherence)
                  ? simulate_traced(dir, n, cs, m, out, dev, dbg_instr, dbg_msg, sched, rounds, nrounds,
                                    micro_file != NULL, micro_seed_given ? &mseed : NULL, weights, write_micro_file,
-                                   metrics, &st)
+                                   metrics, coherence, &st)
                  : dash_simulate_dir(dir, n, cs, m, out, dev, &st);
     free(rounds);
     if (rc == DASH_OK && write_rounds_file &&

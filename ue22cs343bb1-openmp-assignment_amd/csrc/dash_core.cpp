@@ -273,6 +273,7 @@ int dash_run(dash_t* h, dash_stats* stats) {
     if (!h) return DASH_EINVAL;
     if (!h->loaded) return fail(h, DASH_ESTATE, "no traces loaded");
     h->metrics = false;  // dash_compute_metrics' records are the previous run's
+    h->coherence = false;  // and dash_check_coherence's
     dash::SimArgs a = sim_args(h);
     const uint64_t spw = 64 / h->seg;
     HIPCHK(h, hipSetDevice(h->cfg.device));

@@ -248,3 +248,49 @@ int dash_micro_pick(uint64_t seed, uint32_t round, uint32_t enabled, uint64_t we
     }
     return DASH_EINVAL; /* not reached: x < W */
 }
+
+/* The coherence invariants of one system's final state (include/dash.h states them). One scan of
+   the N x CS lines accumulates, per address, the count of copies, of owning copies, the holders,
+   the smallest and largest value and the stale flag; one pass over the addresses forms the bits
+   against the home's directory entry. */
+int dash_check_states(const dash_node_state *nodes, uint32_t num_procs, uint32_t cache_size,
+                      dash_coherence *out, uint32_t *addr_bits) {
+    if (!nodes || !out || num_procs < 1 || num_procs > DASH_MAX_PROCS || cache_size < 1 ||
+        cache_size > DASH_MAX_CACHE)
+        return DASH_EINVAL;
+    enum { A = DASH_MAX_PROCS * DASH_MEM_SIZE };
+    uint8_t n[A] = {0}, own[A] = {0}, mask[A] = {0}, lo[A], hi[A] = {0}, stale[A] = {0};
+    const uint32_t na = num_procs * DASH_MEM_SIZE;
+    memset(lo, 0xFF, sizeof lo);
+    for (uint32_t t = 0; t < num_procs; t++)
+        for (uint32_t i = 0; i < cache_size; i++) {
+            const uint32_t a = nodes[t].cache_addr[i], st = nodes[t].cache_state[i], v = nodes[t].cache_value[i];
+            if (a >= na || st == 3) continue; /* another address, or INVALID */
+            n[a]++;
+            own[a] += st < 2; /* MODIFIED, EXCLUSIVE */
+            mask[a] |= (uint8_t)(1u << t);
+            if (v < lo[a]) lo[a] = (uint8_t)v;
+            if (v > hi[a]) hi[a] = (uint8_t)v;
+            if ((st == 1 || st == 2) && v != nodes[a >> 4].memory[a & 15]) stale[a] = 1;
+        }
+    out->bits = out->addrs = out->first_bits = 0;
+    out->first_addr = 0xFFFFFFFFu;
+    for (uint32_t a = 0; a < na; a++) {
+        const uint32_t d = nodes[a >> 4].dir_state[a & 15], bv = nodes[a >> 4].dir_bitvector[a & 15];
+        uint32_t b = 0;
+        if (own[a] >= 1 && n[a] >= 2) b |= DASH_COH_SWMR;
+        if (d == 2 && n[a] >= 1) b |= DASH_COH_DIR_U_HELD;
+        if (d == 0 && !(n[a] == 1 && own[a] == 1)) b |= DASH_COH_DIR_EM;
+        if (d == 1 && (own[a] >= 1 || n[a] == 0)) b |= DASH_COH_DIR_S;
+        if (d != 2 && (mask[a] & ~bv)) b |= DASH_COH_LOST_SHARER;
+        if (d != 2 && (bv & ~(uint32_t)mask[a])) b |= DASH_COH_STALE_SHARER;
+        if (stale[a]) b |= DASH_COH_STALE_VALUE;
+        if (n[a] >= 2 && lo[a] != hi[a]) b |= DASH_COH_VALUE_SPLIT;
+        if (addr_bits) addr_bits[a] = b;
+        if (!b) continue;
+        if (!out->addrs) out->first_addr = a, out->first_bits = b;
+        out->bits |= b;
+        out->addrs++;
+    }
+    return DASH_OK;
+}

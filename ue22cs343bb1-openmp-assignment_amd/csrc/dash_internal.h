@@ -1,6 +1,7 @@
 // dash_internal.h -- what the host files of libdash share: the handle, the error plumbing and
 // the helpers for device buffers and threads. Internal: not installed, not part of dash.h.
-// (dash_core.cpp, dash_sched.cpp, dash_load.cpp, dash_tools.cpp, dash_metrics.cpp)
+// (dash_core.cpp, dash_sched.cpp, dash_load.cpp, dash_tools.cpp, dash_metrics.cpp,
+// dash_coherence.cpp)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -77,6 +78,10 @@ struct dash_ctx {
     uint8_t* d_metrics_cut = nullptr;            // [num_systems] log shorter than the run
     unsigned long long* d_metrics_tot = nullptr;  // [dash::TOT_WORDS]
     bool metrics = false;                        // the records are those of the last run
+    // dash_check_coherence (dash_coherence.cpp): likewise
+    uint4* d_coh = nullptr;                      // [num_systems] dash_coherence records
+    unsigned long long* d_coh_tot = nullptr;     // [dash::COH_TOT_WORDS]
+    bool coherence = false;                      // the records are those of the last run
     char msg[256] = {0};
     // device-side text ingest (dash_load_text / dash_load_dirs_device): buffers grown on first
     // use and kept, so a repeated load allocates nothing

@@ -17,6 +17,9 @@ libdash:
     Engine.read_state(sys)         -> the nodes' processorNode state
     Engine.compute_metrics()       -> per-node miss / invalidation / wait metrics, reduced on the GPU
                                       from the event log (read_metrics returns the records)
+    Engine.check_coherence()       -> the coherence invariants of every final state, checked on the GPU
+                                      (read_coherence returns the records; check_outcomes classifies
+                                      an explore's outcomes; check_states is the same on the host)
     dump_node(state, node)         -> printProcessorState bytes (:868-902)
     simulate_dir(dir, out_dir)     -> main() end to end
 
@@ -51,6 +54,7 @@ ERR_SCHEDULE = 64  # a micro-step schedule stepped a node with held sends (dash.
 KEEP_STATE = 1
 TIER_FROM_32, TIER_FROM_256 = 2, 4
 TEST_SHORT_ARB = 8  # testing only (dash.h)
+TEST_ONE_GROUP = 16  # testing only (dash.h)
 NUM_TIERS = 3
 GEN_UNIFORM, GEN_CONTENTION, GEN_LOCALITY = 0, 1, 2
 
@@ -65,7 +69,8 @@ EXPORTS = ("dash_create", "dash_destroy", "dash_last_error", "dash_load_traces",
            "dash_load_dirs_device", "dash_read_traces", "dash_ingest_info", "dash_set_system_seeds",
            "dash_broadcast_system", "dash_seed_schedule", "dash_explore", "dash_micro_pick",
            "dash_set_micro_seeds", "dash_read_micro_acts", "dash_explore_micro", "dash_compute_metrics",
-           "dash_read_metrics")
+           "dash_read_metrics", "dash_check_states", "dash_check_coherence", "dash_read_coherence",
+           "dash_check_outcomes")
 TEXT_TILE = 4096  # DASH_TEXT_TILE: bytes per tile of the device text parser
 SIT_OUT = 0xFF
 MICRO_STEP, MICRO_SEND = 0, 1  # dash_set_micro_schedule actions
@@ -151,6 +156,24 @@ class MetricsTotals(ctypes.Structure):
     _fields_ = [(f, ctypes.c_uint64) for f in METRIC_FIELDS + ("systems", "truncated_systems")]
 
 
+# DASH_COH_*: the invariants an address can break (include/dash.h states each)
+COH_SWMR, COH_DIR_U_HELD, COH_DIR_EM, COH_DIR_S = 1, 2, 4, 8
+COH_LOST_SHARER, COH_STALE_SHARER, COH_STALE_VALUE, COH_VALUE_SPLIT = 16, 32, 64, 128
+COH_NAMES = ("SWMR", "DIR_U_HELD", "DIR_EM", "DIR_S", "LOST_SHARER", "STALE_SHARER", "STALE_VALUE", "VALUE_SPLIT")
+COHERENCE_FIELDS = ("bits", "addrs", "first_addr", "first_bits")
+COHERENCE_DTYPE = np.dtype([(f, np.uint32) for f in COHERENCE_FIELDS])
+
+
+class Coherence(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint32) for f in COHERENCE_FIELDS]
+
+
+class CoherenceTotals(ctypes.Structure):
+    _fields_ = [("systems", ctypes.c_uint64), ("violating_systems", ctypes.c_uint64),
+                ("violating_clean_systems", ctypes.c_uint64), ("addrs", ctypes.c_uint64),
+                ("bit_systems", ctypes.c_uint64 * 8), ("bit_addrs", ctypes.c_uint64 * 8)]
+
+
 class Gen(ctypes.Structure):
     _fields_ = [("seed", ctypes.c_uint64), ("sys_base", ctypes.c_uint64), ("kind", ctypes.c_uint32),
                 ("locality", ctypes.c_uint32), ("len", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
@@ -219,6 +242,10 @@ def lib() -> ctypes.CDLL:
         "dash_explore_micro": (i32, [vp, u64, u64, u64, u64, vp, u32, ctypes.POINTER(u32)]),
         "dash_compute_metrics": (i32, [vp, ctypes.POINTER(MetricsTotals)]),
         "dash_read_metrics": (i32, [vp, u64, u64, vp, vp]),
+        "dash_check_states": (i32, [ctypes.POINTER(NodeState), u32, u32, ctypes.POINTER(Coherence), vp]),
+        "dash_check_coherence": (i32, [vp, ctypes.POINTER(CoherenceTotals)]),
+        "dash_read_coherence": (i32, [vp, u64, u64, vp]),
+        "dash_check_outcomes": (i32, [vp, u64, vp, u32, ctypes.POINTER(u64), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -327,6 +354,23 @@ def format_events(events, kinds=(0, 1)) -> str:
             _check(n if n < 0 else OK, "dash_format_event")
             out.append(buf.value.decode())
     return "".join(out)
+
+
+def check_states(nodes, num_procs: int, cache_size: int):
+    """dash_check_states: the coherence invariants of one system's final state on the host. nodes:
+    num_procs NodeState (read_state's list, or states built by hand). Returns (record dict with the
+    COHERENCE_FIELDS, per-address bits uint32 [num_procs * 16])."""
+    arr = (NodeState * max(len(nodes), 1))()
+    for t, s in enumerate(nodes):  # any object with dash_node_state's fields
+        for name, _ in NodeState._fields_:
+            getattr(arr[t], name)[:] = list(getattr(s, name))
+    rec = Coherence()
+    bits = np.zeros(MAX_PROCS * MEM_SIZE, dtype=np.uint32)
+    if len(nodes) < min(num_procs, MAX_PROCS):
+        raise ValueError("check_states: fewer states than num_procs")
+    _check(lib().dash_check_states(arr, num_procs, cache_size, ctypes.byref(rec), bits.ctypes.data),
+           "dash_check_states")
+    return {f: int(getattr(rec, f)) for f in COHERENCE_FIELDS}, bits[:num_procs * MEM_SIZE].copy()
 
 
 def seed_schedule(seed: int, num_procs: int, rounds: int) -> np.ndarray:
@@ -644,6 +688,38 @@ class Engine:
         _check(lib().dash_read_metrics(self.h, first, count, out.ctypes.data, flags.ctypes.data),
                "dash_read_metrics", self.h)
         return rec, cut
+
+    def check_coherence(self) -> dict:
+        """dash_check_coherence: one GPU pass over the batch's final state of the last run (needs
+        keep_state). Returns the totals: systems, violating_systems, violating_clean_systems (bits set
+        and no DASH_ERR_* bit), addrs, and bit_systems / bit_addrs, lists of 8 in COH_NAMES' order.
+        The per-system records stay on the device for read_coherence until the next run."""
+        t = CoherenceTotals()
+        _check(lib().dash_check_coherence(self.h, ctypes.byref(t)), "dash_check_coherence", self.h)
+        return {"systems": int(t.systems), "violating_systems": int(t.violating_systems),
+                "violating_clean_systems": int(t.violating_clean_systems), "addrs": int(t.addrs),
+                "bit_systems": [int(x) for x in t.bit_systems], "bit_addrs": [int(x) for x in t.bit_addrs]}
+
+    def read_coherence(self, first=0, count=None) -> np.ndarray:
+        """dash_read_coherence: the records of systems [first, first + count), a structured array
+        [count] with the COHERENCE_FIELDS."""
+        count = self.num_systems - first if count is None else count
+        rec = np.zeros(max(count, 0), dtype=COHERENCE_DTYPE)
+        out = rec if rec.size else np.zeros(1, dtype=COHERENCE_DTYPE)  # non-null for an empty window
+        _check(lib().dash_read_coherence(self.h, first, count, out.ctypes.data), "dash_read_coherence", self.h)
+        return rec
+
+    def check_outcomes(self, src: int, outcomes, weights=None) -> np.ndarray:
+        """dash_check_outcomes: the coherence record of every outcome explore (weights None) or
+        explore_micro (its weight vector; MICRO_UNIFORM for its default) returned, by re-running the
+        witness seeds: a structured array [len(outcomes)] with the COHERENCE_FIELDS."""
+        arr = (Outcome * max(len(outcomes), 1))(*[Outcome(**{f: o[f] for f, _ in Outcome._fields_}) for o in outcomes])
+        rec = np.zeros(len(outcomes), dtype=COHERENCE_DTYPE)
+        out = rec if rec.size else np.zeros(1, dtype=COHERENCE_DTYPE)
+        w = None if weights is None else ctypes.byref(ctypes.c_uint64(pack_weights(weights)))
+        _check(lib().dash_check_outcomes(self.h, src, arr, len(outcomes), w, out.ctypes.data),
+               "dash_check_outcomes", self.h)
+        return rec
 
     def stream(self) -> int:
         return int(lib().dash_stream(self.h) or 0)
