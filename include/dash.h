@@ -85,6 +85,10 @@ enum dash_txn {
                                   so later rounds take the in-kernel hashing path */
 #define DASH_TEST_ONE_GROUP 16u /* testing only: dash_check_coherence walks the batch with a single
                                    workgroup, so a small batch takes several trips of its loop */
+#define DASH_TEST_INSERT_PER_LANE 32u /* testing and measurement only: dash_explore_sources inserts every
+                                        system's outcome on its own, without grouping equal keys of a wave */
+#define DASH_TEST_INSERT_GROUPS 64u   /* likewise: every distinct key of a wave is inserted as a group, however
+                                        many there are (the default groups the first few) */
 
 typedef struct dash_cfg {
     uint32_t num_procs;   /* NUM_PROCS (ref :6): 4 or 8 */
@@ -424,6 +428,57 @@ int dash_read_coherence(dash_t *h, uint64_t first, uint64_t count, dash_coherenc
    explore, plus DASH_KEEP_STATE. Afterwards the handle holds the last pass. */
 int dash_check_outcomes(dash_t *h, uint64_t src, const dash_outcome *outs, uint32_t n,
                         const uint64_t *weights, dash_coherence *out /* [n] */);
+
+/* ---- many trace sets at once: outcomes merged and classified on the device
+   (csrc/dash_outcomes.hip) ----
+   The sources are systems 0 .. num_sources - 1 of the loaded batch. Every source runs
+   seeds_per_source schedules, seeds first_seed + j, under seeded round schedules (weights == NULL; seed
+   0 is lockstep, as in dash_explore) or seeded micro-step schedules under the one vector *weights. The
+   systems of a pass are assigned by dash_explore_assign (below) with S = cfg.num_systems: system k >=
+   num_sources is overwritten by a copy of system k % num_sources on the device, the seeds of a pass are
+   written on the device, and after each pass every counted system's (source, digest, errors) goes into
+   a device hash table of table_slots slots (a power of two; another value is rounded up; 0 =
+   next_pow2(2 * min(num_sources * seeds_per_source, 2^21)), at least 64). Keys are compared in full:
+   two sources never share an entry, even with identical traces. dash_check_coherence's launch then
+   runs over the pass's final states and every outcome's witness, the lowest seed that reached it, leaves
+   its rounds and its coherence record in the table. Only the compacted table crosses to the host.
+
+   Outcomes come back ordered by (source, witness seed): up to cap into out, their number into *n, which
+   may exceed cap (cap 0 with out NULL: count only). per_source[i] (optional) and *totals (optional)
+   are sums over the whole list, not just its first cap entries.
+
+   Handle requirements as the matching explore (created with schedule_seed != 0, loaded, and for
+   weights == NULL not following a micro-step table) plus DASH_KEEP_STATE: DASH_ESTATE otherwise.
+   DASH_EINVAL: num_sources 0 or above cfg.num_systems, a weight byte above 31, first_seed +
+   seeds_per_source wrapping 2^64, out == NULL with cap != 0, n == NULL. Afterwards the handle holds the
+   last pass (its seeds stay set; states, results and coherence records are readable).
+
+   A table that fills: a key is placed on its first insert or never (slots are never freed), so what is
+   returned is exact for the keys it lists, totals->unplaced counts the schedules that found no slot,
+   sum of count + unplaced == schedules, and the return code is DASH_ETRUNC (out, *n, per_source and
+   totals are filled). With the default size and at most 2^21 schedules this cannot happen. */
+typedef struct dash_outcome_ex {
+    dash_outcome o;      /* digest, count, seed (lowest that reached it), rounds, errors of that witness */
+    dash_coherence coh;  /* the invariants of that final state */
+    uint32_t source, _reserved;
+} dash_outcome_ex;       /* 56 B */
+typedef struct dash_source_summary {
+    uint64_t schedules, incoherent_schedules;   /* counted; those whose outcome has coh.bits != 0 */
+    uint64_t top_count;                         /* count of the most frequent outcome */
+    uint32_t outcomes, incoherent_outcomes, coh_bits /* OR */, err_bits /* OR */;
+} dash_source_summary;
+typedef struct dash_explore_totals {
+    uint64_t schedules, outcomes, unplaced, passes, table_slots;
+    uint64_t incoherent_outcomes, incoherent_schedules, incoherent_clean_schedules; /* clean: errors == 0 */
+    uint64_t bit_schedules[8];                  /* schedules whose outcome has DASH_COH bit 1<<k */
+    double sim_ms, merge_ms;                    /* device events: dash_run's kernels; the kernels of
+                                                   dash_outcomes.hip + the coherence launch */
+    double insert_ms;                           /* of merge_ms: the insert kernels alone */
+} dash_explore_totals;
+int dash_explore_sources(dash_t *h, uint64_t num_sources, uint64_t first_seed, uint64_t seeds_per_source,
+                         const uint64_t *weights, uint64_t table_slots, dash_outcome_ex *out, uint64_t cap,
+                         uint64_t *n, dash_source_summary *per_source /* [num_sources] or NULL */,
+                         dash_explore_totals *totals /* or NULL */);
 /* HIP stream the engine launches on (hipStream_t as void*) */
 void *dash_stream(dash_t *h);
 
@@ -456,6 +511,19 @@ int dash_probe_box(int device, dash_box_probe *out);
    the run's rounds reproduces the run; it can be read, edited and kept (tests/golden/schedules/).
    DASH_EINVAL for num_procs outside 1..8 or sched == NULL. */
 int dash_seed_schedule(uint64_t seed, uint32_t num_procs, uint32_t rounds, uint8_t *sched);
+/* Which source and seed system k of a pass of dash_explore_sources runs, and whether its outcome is
+   counted: the rule the device follows, stated once. A handle of S systems explores G sources
+   (1 <= G <= S) with K seeds each, F the first seed (F + K must not wrap 2^64):
+     - R = S / G seeds of every source run per pass; there are ceil(K / R) passes;
+     - in pass p, system k runs source k % G;
+     - its seed index is j = p * R + k / G, its seed F + j;
+     - it is counted iff k < G * R and j < K;
+     - an uncounted system runs a repeat, seed index p * R + (k / G) % fresh with
+       fresh = min(R, K - p * R), and is never counted.
+   *source, *seed and *counted (each optional) are set for system k < S of pass `pass` < ceil(K / R);
+   DASH_EINVAL outside these ranges. Pure host code. */
+int dash_explore_assign(uint64_t S, uint64_t G, uint64_t K, uint64_t F, uint64_t pass, uint64_t k,
+                        uint32_t *source, uint64_t *seed, int *counted);
 /* initializeProcessor's parse (ref :822-850): up to max_instr records into out[]. */
 int dash_parse_core_file(const char *path, uint32_t num_procs, uint32_t max_instr,
                          uint16_t *out, uint32_t *len);

@@ -220,6 +220,34 @@ static void micro_picks(void) {
           "micro_pick argument checks");
 }
 
+/* dash_explore_assign at the edges of 64-bit arithmetic (the undefined-behaviour sanitizer sees a
+   wrapped signed value or an out-of-range shift; unsigned wraps are checked by hand): a counted
+   system's seed lies in [F, F + K), a repeat's in its own pass, and the refusals hold */
+static void explore_assigns(void) {
+    for (int it = 0; it < 20000; it++) {
+        const uint64_t S = 1 + rnd() % (it & 1 ? 70 : 0xFFFFFFFFull), G = 1 + rnd() % S;
+        const uint64_t K = it % 3 ? 1 + rnd() % 100000 : rnd() >> (1 + rnd() % 63), F = it & 2 ? UINT64_MAX - K : rnd() % (UINT64_MAX - K);
+        const uint64_t R = S / G, passes = K / R + (K % R != 0);
+        if (!passes) {
+            CHECK(dash_explore_assign(S, G, K, F, 0, 0, NULL, NULL, NULL) == DASH_EINVAL, "assign: no pass it %d", it);
+            continue;
+        }
+        const uint64_t p = it & 4 ? passes - 1 : rnd() % passes, k = it & 8 ? S - 1 : rnd() % S;
+        uint32_t src = 0;
+        uint64_t seed = 0;
+        int counted = -1;
+        CHECK(dash_explore_assign(S, G, K, F, p, k, &src, &seed, &counted) == DASH_OK, "assign it %d", it);
+        CHECK(src == k % G && seed >= F && seed - F < K && seed - F >= p * R && seed - F - p * R < R, "assign range it %d", it);
+        CHECK(counted == (k < G * R && p * R + k / G < K) && (!counted || seed - F == p * R + k / G), "assign counted it %d", it);
+        CHECK(dash_explore_assign(S, G, K, F, passes, k, &src, &seed, &counted) == DASH_EINVAL &&
+                  dash_explore_assign(S, G, K, F, p, S, &src, &seed, &counted) == DASH_EINVAL, "assign refusals it %d", it);
+    }
+    CHECK(dash_explore_assign(8, 0, 1, 0, 0, 0, NULL, NULL, NULL) == DASH_EINVAL &&
+              dash_explore_assign(8, 9, 1, 0, 0, 0, NULL, NULL, NULL) == DASH_EINVAL &&
+              dash_explore_assign(8, 1, 2, UINT64_MAX - 1, 0, 0, NULL, NULL, NULL) == DASH_EINVAL,
+          "assign argument checks");
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s SCRATCH_DIR GOLDEN_DIR...\n", argv[0]);
@@ -230,6 +258,7 @@ int main(int argc, char **argv) {
     random_systems();
     seed_schedules();
     micro_picks();
+    explore_assigns();
     if (failures) fprintf(stderr, "%d check(s) failed\n", failures);
     else printf("host sanitizer run clean\n");
     return failures ? 1 : 0;

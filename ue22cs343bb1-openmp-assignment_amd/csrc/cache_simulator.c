@@ -53,6 +53,12 @@
  *       S0 + K - 1 (S0 = --micro-seed, default 0) under one weight vector (dash_explore_micro);
  *       same output lines (`--micro-seed <seed> --weights ...` then writes that state's dumps):
  *       e.g. `test_4 --explore-micro 250 --weights 4,0,31,1` lists the accepted run_3
+ *   --sources FILE    with --explore / --explore-micro: several trace directories in one call
+ *       (dash_explore_sources). <test_directory> is source 0, FILE lists the others, one per line; K
+ *       schedules of every source run side by side in the batch and their outcomes are merged and
+ *       classified on the GPU. Prints the outcome lines with a leading source-index column, ordered by
+ *       (source, seed) (--coherence adds the same last column), then per source one line "source <i>
+ *       <dir> outcomes=<n> schedules=<K> incoherent=<schedules whose final state breaks an invariant>"
  *
  * Bulk modes (one GPU batch, many systems; dumps go to OUT_DIR/<k>/):
  *   --batch LIST        system k = the k-th trace directory listed in LIST (one per line)
@@ -406,6 +412,92 @@ static int explore_dir(const char *dir, unsigned n, unsigned cs, unsigned m, int
     return rc;
 }
 
+/* --explore K / --explore-micro K with --sources FILE: the outcomes of several trace directories in one
+   call (dash_explore_sources). dir is source 0; FILE lists the others, one per line. */
+static int explore_sources_dirs(const char *dir, const char *list, unsigned n, unsigned cs, unsigned m, int dev,
+                                unsigned long long k, unsigned long long s0, const uint64_t *weights, int coherence) {
+    FILE *f = fopen(list, "r");
+    if (!f || n < 1 || n > DASH_MAX_PROCS) {
+        fprintf(stderr, "Error: could not open %s\n", list);
+        if (f) fclose(f);
+        return f ? DASH_EINVAL : DASH_EIO;
+    }
+    size_t g = 1, gcap = 16;
+    char **dirs = (char **)malloc(gcap * sizeof *dirs), line[4096];
+    int rc = dirs ? DASH_OK : DASH_ENOMEM;
+    if (dirs) dirs[0] = strdup(dir);
+    while (rc == DASH_OK && fgets(line, sizeof line, f)) {
+        line[strcspn(line, "\r\n")] = 0;
+        if (!line[0]) continue;
+        if (g == gcap) {
+            char **grown = (char **)realloc(dirs, (gcap *= 2) * sizeof *dirs);
+            if (!grown) rc = DASH_ENOMEM;
+            else dirs = grown;
+        }
+        if (rc == DASH_OK && !(dirs[g++] = strdup(line))) rc = DASH_ENOMEM;
+    }
+    fclose(f);
+    /* a handle of up to 65,536 systems, at least one per source; only the sources' rows are filled on the
+       host (the call copies them over the others on the device); the buffer stays below 64 MB when the
+       sources allow it */
+    const size_t stride = m ? m : 1, row = (size_t)n * stride;
+    uint64_t nsys = k && g * k < 65536 ? g * k : 65536;
+    if (nsys > (64u << 20) / (row * 2)) nsys = (64u << 20) / (row * 2);
+    if (nsys < g) nsys = g;
+    uint16_t *tr = rc == DASH_OK ? (uint16_t *)calloc(nsys * row, sizeof *tr) : NULL;
+    uint32_t *lens = rc == DASH_OK ? (uint32_t *)calloc(nsys * n, sizeof *lens) : NULL;
+    if (rc == DASH_OK && (!tr || !lens)) rc = DASH_ENOMEM;
+    for (size_t s = 0; rc == DASH_OK && s < g; s++) {
+        char base[4096], path[4200];
+        if ((rc = dash_resolve_dir(dirs[s], base, sizeof base)) != DASH_OK)
+            fprintf(stderr, "Error: could not open %s/core_0.txt\n", base);
+        for (unsigned t = 0; rc == DASH_OK && t < n; t++) {
+            snprintf(path, sizeof path, "%s/core_%u.txt", base, t);
+            rc = dash_parse_core_file(path, n, m, tr + (s * n + t) * stride, &lens[s * n + t]);
+        }
+    }
+    dash_t *h = NULL;
+    dash_cfg cfg = {0};
+    cfg.num_procs = n;
+    cfg.cache_size = cs;
+    cfg.max_instr = m;
+    cfg.num_systems = nsys;
+    cfg.device = dev;
+    cfg.schedule_seed = 1; /* any seeded handle: every system gets a seed of its own */
+    cfg.flags = DASH_KEEP_STATE; /* the outcomes are classified from the final states of the passes */
+    if (rc == DASH_OK && (rc = dash_create(&cfg, &h)) == DASH_OK &&
+        (rc = dash_load_traces(h, tr, stride, lens, nsys)) == DASH_OK) {
+        uint64_t total = 0, cap = 4096;
+        dash_outcome_ex *o = (dash_outcome_ex *)malloc(cap * sizeof *o);
+        dash_source_summary *per = (dash_source_summary *)calloc(g, sizeof *per);
+        rc = o && per ? dash_explore_sources(h, g, s0, k, weights, 0, o, cap, &total, per, NULL) : DASH_ENOMEM;
+        if (rc == DASH_OK && total > cap) { /* rare: once more, with room for all of them */
+            cap = total;
+            free(o);
+            o = (dash_outcome_ex *)malloc((size_t)cap * sizeof *o);
+            rc = o ? dash_explore_sources(h, g, s0, k, weights, 0, o, cap, &total, per, NULL) : DASH_ENOMEM;
+        }
+        for (uint64_t i = 0; rc == DASH_OK && i < total && i < cap; i++) {
+            printf("%u %016llx %llu %llu %u %x", o[i].source, (unsigned long long)o[i].o.digest,
+                   (unsigned long long)o[i].o.count, (unsigned long long)o[i].o.seed, o[i].o.rounds, o[i].o.errors);
+            if (coherence) printf(" %x", o[i].coh.bits);
+            printf("\n");
+        }
+        for (size_t s = 0; rc == DASH_OK && s < g; s++)
+            printf("source %zu %s outcomes=%u schedules=%llu incoherent=%llu\n", s, dirs[s], per[s].outcomes,
+                   (unsigned long long)per[s].schedules, (unsigned long long)per[s].incoherent_schedules);
+        free(per);
+        free(o);
+    }
+    if (rc != DASH_OK && h) fprintf(stderr, "%s\n", dash_last_error(h));
+    dash_destroy(h);
+    free(tr);
+    free(lens);
+    for (size_t s = 0; dirs && s < g; s++) free(dirs[s]);
+    free(dirs);
+    return rc;
+}
+
 typedef struct {
     unsigned n, cs, m, len, kind, locality;
     unsigned long long seed, sched;
@@ -535,7 +627,8 @@ int main(int argc, char *argv[]) {
     unsigned n = 4, cs = 4, m = 32;
     int dev = 0, show = 0, dbg_instr = 0, dbg_msg = 0, n_given = 0, device_ingest = 0;
     const char *out = ".", *dir = NULL, *batch = NULL, *digests = NULL, *dump = NULL, *rounds_file = NULL,
-               *micro_file = NULL, *write_rounds_file = NULL, *write_micro_file = NULL, *weights_text = NULL;
+               *micro_file = NULL, *write_rounds_file = NULL, *write_micro_file = NULL, *weights_text = NULL,
+               *sources_file = NULL;
     unsigned long long synth = 0, seed = 0x5EED, sched = 0, explore = 0, micro_seed = 0;
     int explore_given = 0, explore_micro = 0, micro_seed_given = 0, metrics = 0, coherence = 0;
     uint64_t weights = DASH_MICRO_UNIFORM;
@@ -568,6 +661,7 @@ int main(int argc, char *argv[]) {
             explore = strtoull(argv[++i], NULL, 0), explore_given = explore_micro = 1;
         else if (!strcmp(argv[i], "--micro-seed") && i + 1 < argc) micro_seed = strtoull(argv[++i], NULL, 0), micro_seed_given = 1;
         else if (!strcmp(argv[i], "--weights") && i + 1 < argc) weights_text = argv[++i];
+        else if (!strcmp(argv[i], "--sources") && i + 1 < argc) sources_file = argv[++i];
         else if (!strcmp(argv[i], "--write-micro") && i + 1 < argc) write_micro_file = argv[++i];
         else if (!strcmp(argv[i], "--locality") && i + 1 < argc) loc = atof(argv[++i]);
         else if (!strcmp(argv[i], "--kind") && i + 1 < argc) {
@@ -599,14 +693,20 @@ int main(int argc, char *argv[]) {
         fprintf(stderr, "cache_simulator: --weights goes with --micro-seed or --explore-micro\n");
         return EXIT_FAILURE;
     }
+    if (sources_file && !explore_given) {
+        fprintf(stderr, "cache_simulator: --sources goes with --explore or --explore-micro\n");
+        return EXIT_FAILURE;
+    }
     if (explore_given) {
         if (rounds_file || micro_file || write_rounds_file || write_micro_file || metrics) {
             fprintf(stderr, "cache_simulator: --explore takes no --rounds, --micro, --write-rounds, --write-micro "
                             "or --metrics\n");
             return EXIT_FAILURE;
         }
-        int rc = explore_dir(dir, n, cs, m, dev, explore, explore_micro ? micro_seed : sched,
-                             explore_micro ? &weights : NULL, coherence);
+        const unsigned long long s0 = explore_micro ? micro_seed : sched;
+        const uint64_t *w = explore_micro ? &weights : NULL;
+        int rc = sources_file ? explore_sources_dirs(dir, sources_file, n, cs, m, dev, explore, s0, w, coherence)
+                              : explore_dir(dir, n, cs, m, dev, explore, s0, w, coherence);
         if (rc != DASH_OK) {
             const char *why = dash_last_error(NULL);
             fprintf(stderr, "cache_simulator: %s (%d)\n", why[0] ? why : "failed", rc);

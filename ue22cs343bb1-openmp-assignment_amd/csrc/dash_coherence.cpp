@@ -11,38 +11,45 @@ static_assert(offsetof(dash_coherence_totals, bit_systems) == dash::COH_BIT_SYST
                   offsetof(dash_coherence_totals, bit_addrs) == dash::COH_BIT_ADDRS * sizeof(uint64_t),
               "the per-bit counts' words");
 
+// dash_check_coherence up to the launch (dash_internal.h): state checks, buffers on first use, the
+// totals' memset and the kernel, all enqueued on the handle's stream
+int coherence_enqueue(dash_t* h) {
+    if (!h->ran) return fail(h, DASH_ESTATE, "dash_run has not completed");
+    if (!h->d_state) return fail(h, DASH_ESTATE, "created without DASH_KEEP_STATE");
+    const uint64_t nsys = h->cfg.num_systems;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (!h->d_coh) {
+        hipError_t e = buf_alloc(h, h->d_coh, nsys);
+        if (e == hipSuccess) e = buf_alloc(h, h->d_coh_tot, dash::COH_TOT_WORDS);
+        if (e != hipSuccess) {
+            buf_free(h, h->d_coh);
+            buf_free(h, h->d_coh_tot);
+            return hip_fail(h, e, "hipMalloc(coherence)");
+        }
+    }
+    h->coherence = false;
+    dash::CoherenceArgs a{};
+    a.state = h->d_state;
+    a.errors = h->d_errors;
+    a.nsys = nsys;
+    a.num_procs = h->cfg.num_procs;
+    a.seg = h->seg;
+    a.cache_size = h->cfg.cache_size;
+    a.max_grid = (h->cfg.flags & DASH_TEST_ONE_GROUP) ? 1u : 0u;
+    a.records = h->d_coh;
+    a.totals = h->d_coh_tot;
+    HIPCHK(h, hipMemsetAsync(h->d_coh_tot, 0, dash::COH_TOT_WORDS * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, dash::launch_coherence(a, h->groups, h->stream));
+    return DASH_OK;
+}
+
 extern "C" {
 
 int dash_check_coherence(dash_t* h, dash_coherence_totals* totals) {
     return guarded(h, "dash_check_coherence", [&]() -> int {
         if (!h) return DASH_EINVAL;
-        if (!h->ran) return fail(h, DASH_ESTATE, "dash_run has not completed");
-        if (!h->d_state) return fail(h, DASH_ESTATE, "created without DASH_KEEP_STATE");
-        const uint64_t nsys = h->cfg.num_systems;
-        HIPCHK(h, hipSetDevice(h->cfg.device));
-        if (!h->d_coh) {
-            hipError_t e = buf_alloc(h, h->d_coh, nsys);
-            if (e == hipSuccess) e = buf_alloc(h, h->d_coh_tot, dash::COH_TOT_WORDS);
-            if (e != hipSuccess) {
-                buf_free(h, h->d_coh);
-                buf_free(h, h->d_coh_tot);
-                return hip_fail(h, e, "hipMalloc(coherence)");
-            }
-        }
-        h->coherence = false;
-        dash::CoherenceArgs a{};
-        a.state = h->d_state;
-        a.errors = h->d_errors;
-        a.nsys = nsys;
-        a.num_procs = h->cfg.num_procs;
-        a.seg = h->seg;
-        a.cache_size = h->cfg.cache_size;
-        a.max_grid = (h->cfg.flags & DASH_TEST_ONE_GROUP) ? 1u : 0u;
-        a.records = h->d_coh;
-        a.totals = h->d_coh_tot;
+        if (int rc = coherence_enqueue(h)) return rc;
         unsigned long long t[dash::COH_TOT_WORDS];
-        HIPCHK(h, hipMemsetAsync(h->d_coh_tot, 0, sizeof t, h->stream));
-        HIPCHK(h, dash::launch_coherence(a, h->groups, h->stream));
         HIPCHK(h, hipMemcpyAsync(t, h->d_coh_tot, sizeof t, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         h->coherence = true;

@@ -249,6 +249,22 @@ int dash_micro_pick(uint64_t seed, uint32_t round, uint32_t enabled, uint64_t we
     return DASH_EINVAL; /* not reached: x < W */
 }
 
+/* Which (source, seed) system k runs in one pass of dash_explore_sources, and whether it is counted
+   (include/dash.h states the rule; the device's twin is fill_seeds in csrc/dash_outcomes.hip). */
+int dash_explore_assign(uint64_t S, uint64_t G, uint64_t K, uint64_t F, uint64_t pass, uint64_t k,
+                        uint32_t *source, uint64_t *seed, int *counted) {
+    if (G < 1 || G > S || G > 0xFFFFFFFFull || K > UINT64_MAX - F || k >= S) return DASH_EINVAL;
+    const uint64_t R = S / G;
+    if (pass >= K / R + (K % R != 0)) return DASH_EINVAL;
+    const uint64_t base = pass * R, row = k / G; /* base < K: no wrap */
+    const uint64_t fresh = K - base < R ? K - base : R;
+    const int is_counted = row < R && row < fresh;
+    if (source) *source = (uint32_t)(k % G);
+    if (seed) *seed = F + base + (is_counted ? row : row % fresh);
+    if (counted) *counted = is_counted;
+    return DASH_OK;
+}
+
 /* The coherence invariants of one system's final state (include/dash.h states them). One scan of
    the N x CS lines accumulates, per address, the count of copies, of owning copies, the holders,
    the smallest and largest value and the stale flag; one pass over the addresses forms the bits

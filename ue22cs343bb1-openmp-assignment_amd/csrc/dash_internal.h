@@ -1,7 +1,7 @@
 // dash_internal.h -- what the host files of libdash share: the handle, the error plumbing and
 // the helpers for device buffers and threads. Internal: not installed, not part of dash.h.
 // (dash_core.cpp, dash_sched.cpp, dash_load.cpp, dash_tools.cpp, dash_metrics.cpp,
-// dash_coherence.cpp)
+// dash_coherence.cpp, dash_outcomes.cpp)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -82,6 +82,15 @@ struct dash_ctx {
     uint4* d_coh = nullptr;                      // [num_systems] dash_coherence records
     unsigned long long* d_coh_tot = nullptr;     // [dash::COH_TOT_WORDS]
     bool coherence = false;                      // the records are those of the last run
+    // dash_explore_sources (dash_outcomes.cpp): allocated by the call, kept and reused while they fit
+    void* d_oc_table = nullptr;                  // [oc_slots] dash::OutcomeSlot
+    uint64_t oc_slots = 0;
+    void* d_oc_out = nullptr;                    // [oc_out_cap] compacted entries (dash_outcome_ex)
+    uint64_t oc_out_cap = 0;
+    uint32_t* d_oc_place = nullptr;              // [num_systems] the slot of every system of the pass
+    unsigned long long* d_oc_counters = nullptr;  // [dash::OC_WORDS]
+    hipEvent_t oc_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // around the kernels before / after
+                                                                          // dash_run, and after the insert
     char msg[256] = {0};
     // device-side text ingest (dash_load_text / dash_load_dirs_device): buffers grown on first
     // use and kept, so a repeated load allocates nothing
@@ -154,6 +163,10 @@ inline hipError_t reset_hint(dash_t* h) {
     h->hint_tier = -1;
     return hipMemsetAsync(h->d_skip, 0, std::max<uint64_t>(h->cfg.num_systems, 1), h->stream);
 }
+
+// dash_check_coherence up to and including its launch, without the copy of the totals and the wait
+// (dash_coherence.cpp); the caller sets h->coherence once the stream has passed it
+int coherence_enqueue(dash_t* h);
 
 // message of the last failed handle-less call (dash_create, dash_run_host_batched, ...) on this thread
 inline thread_local char g_msg[256] = "";

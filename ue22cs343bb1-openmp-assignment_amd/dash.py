@@ -14,6 +14,9 @@ libdash:
     Engine.run()                   -> the OpenMP parallel region (:149-738)
     Engine.explore(src, s0, k)     -> the outcomes k seeded legal schedules of one system reach
     Engine.explore_micro(src, s0, k, weights) -> the same over seeded micro-step schedules
+    Engine.explore_sources(g, s0, k) -> the outcomes of g trace sets at once, merged and classified on
+                                      the GPU (counts, witnesses, coherence records; explore_assign
+                                      states which system runs which source and seed)
     Engine.read_state(sys)         -> the nodes' processorNode state
     Engine.compute_metrics()       -> per-node miss / invalidation / wait metrics, reduced on the GPU
                                       from the event log (read_metrics returns the records)
@@ -55,6 +58,7 @@ KEEP_STATE = 1
 TIER_FROM_32, TIER_FROM_256 = 2, 4
 TEST_SHORT_ARB = 8  # testing only (dash.h)
 TEST_ONE_GROUP = 16  # testing only (dash.h)
+TEST_INSERT_PER_LANE, TEST_INSERT_GROUPS = 32, 64  # testing and measurement only (dash.h)
 NUM_TIERS = 3
 GEN_UNIFORM, GEN_CONTENTION, GEN_LOCALITY = 0, 1, 2
 
@@ -70,7 +74,7 @@ EXPORTS = ("dash_create", "dash_destroy", "dash_last_error", "dash_load_traces",
            "dash_broadcast_system", "dash_seed_schedule", "dash_explore", "dash_micro_pick",
            "dash_set_micro_seeds", "dash_read_micro_acts", "dash_explore_micro", "dash_compute_metrics",
            "dash_read_metrics", "dash_check_states", "dash_check_coherence", "dash_read_coherence",
-           "dash_check_outcomes")
+           "dash_check_outcomes", "dash_explore_sources", "dash_explore_assign")
 TEXT_TILE = 4096  # DASH_TEXT_TILE: bytes per tile of the device text parser
 SIT_OUT = 0xFF
 MICRO_STEP, MICRO_SEND = 0, 1  # dash_set_micro_schedule actions
@@ -174,6 +178,30 @@ class CoherenceTotals(ctypes.Structure):
                 ("bit_systems", ctypes.c_uint64 * 8), ("bit_addrs", ctypes.c_uint64 * 8)]
 
 
+# dash_outcome_ex / dash_source_summary / dash_explore_totals (dash_explore_sources): an outcome with
+# its coherence record (the COHERENCE_FIELDS, flat) and its source
+OUTCOME_EX_DTYPE = np.dtype([("digest", np.uint64), ("count", np.uint64), ("seed", np.uint64), ("rounds", np.uint32),
+                             ("errors", np.uint32)] + [(f, np.uint32) for f in COHERENCE_FIELDS] +
+                            [("source", np.uint32), ("_reserved", np.uint32)])
+SOURCE_SUMMARY_DTYPE = np.dtype([("schedules", np.uint64), ("incoherent_schedules", np.uint64),
+                                 ("top_count", np.uint64), ("outcomes", np.uint32),
+                                 ("incoherent_outcomes", np.uint32), ("coh_bits", np.uint32), ("err_bits", np.uint32)])
+assert OUTCOME_EX_DTYPE.itemsize == 56 and SOURCE_SUMMARY_DTYPE.itemsize == 40
+
+
+class ExploreTotals(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint64) for f in ("schedules", "outcomes", "unplaced", "passes", "table_slots",
+                                               "incoherent_outcomes", "incoherent_schedules",
+                                               "incoherent_clean_schedules")] + \
+               [("bit_schedules", ctypes.c_uint64 * 8), ("sim_ms", ctypes.c_double), ("merge_ms", ctypes.c_double),
+                ("insert_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        d = {f: getattr(self, f) for f, _ in self._fields_}
+        d["bit_schedules"] = [int(x) for x in self.bit_schedules]
+        return d
+
+
 class Gen(ctypes.Structure):
     _fields_ = [("seed", ctypes.c_uint64), ("sys_base", ctypes.c_uint64), ("kind", ctypes.c_uint32),
                 ("locality", ctypes.c_uint32), ("len", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
@@ -246,6 +274,10 @@ def lib() -> ctypes.CDLL:
         "dash_check_coherence": (i32, [vp, ctypes.POINTER(CoherenceTotals)]),
         "dash_read_coherence": (i32, [vp, u64, u64, vp]),
         "dash_check_outcomes": (i32, [vp, u64, vp, u32, ctypes.POINTER(u64), vp]),
+        "dash_explore_sources": (i32, [vp, u64, u64, u64, ctypes.POINTER(u64), u64, vp, u64, ctypes.POINTER(u64), vp,
+                                       ctypes.POINTER(ExploreTotals)]),
+        "dash_explore_assign": (i32, [u64, u64, u64, u64, u64, u64, ctypes.POINTER(u32), ctypes.POINTER(u64),
+                                      ctypes.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -402,6 +434,15 @@ def micro_pick(seed: int, round: int, enabled: int, weights, num_procs: int) -> 
     t = lib().dash_micro_pick(seed, round, enabled, pack_weights(weights), num_procs)
     _check(t if t < 0 else OK, "dash_micro_pick")
     return t
+
+
+def explore_assign(S: int, G: int, K: int, F: int, pass_: int, k: int):
+    """dash_explore_assign: (source, seed, counted) of system k in pass `pass_` of an explore_sources
+    call with G sources and K seeds per source from F on a handle of S systems."""
+    src, seed, counted = ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_int()
+    _check(lib().dash_explore_assign(S, G, K, F, pass_, k, ctypes.byref(src), ctypes.byref(seed),
+                                     ctypes.byref(counted)), "dash_explore_assign")
+    return src.value, seed.value, bool(counted.value)
 
 
 def probe_box(device=0) -> dict:
@@ -630,6 +671,34 @@ class Engine:
         cap = want
         self.explore_total = int(n.value)
         return [{f: int(getattr(o, f)) for f, _ in Outcome._fields_} for o in arr[:min(n.value, cap)]]
+
+    def explore_sources(self, num_sources: int, first_seed: int, seeds_per_source: int, weights=None,
+                        table_slots=0, cap=None):
+        """dash_explore_sources: systems 0 .. num_sources - 1 are the sources; every one runs
+        seeds_per_source schedules from first_seed (weights None: seeded round schedules; else seeded
+        micro-step schedules under that vector, MICRO_UNIFORM for uniform). Returns (outcomes, a
+        structured array with OUTCOME_EX_DTYPE ordered by (source, witness seed); per_source, one
+        SOURCE_SUMMARY_DTYPE record per source; totals dict). cap=k keeps the first k outcomes. The
+        result also stays on the engine as explore_sources_result; when the table filled it is stored
+        there before DashError(ETRUNC) is raised."""
+        want = min(max(num_sources * seeds_per_source, 1), 1 << 22) if cap is None else cap
+        w = None if weights is None else ctypes.byref(ctypes.c_uint64(pack_weights(weights)))
+        per = np.zeros(max(num_sources, 0), dtype=SOURCE_SUMMARY_DTYPE)
+        per_buf = per if per.size else np.zeros(1, dtype=SOURCE_SUMMARY_DTYPE)
+        while True:
+            outs = np.zeros(max(want, 1), dtype=OUTCOME_EX_DTYPE)
+            tot, n = ExploreTotals(), ctypes.c_uint64()
+            rc = lib().dash_explore_sources(self.h, num_sources, first_seed, seeds_per_source, w, table_slots,
+                                            outs.ctypes.data, want, ctypes.byref(n), per_buf.ctypes.data,
+                                            ctypes.byref(tot))
+            if rc not in (OK, ETRUNC) or cap is not None or n.value <= want:
+                break
+            want = n.value  # more outcomes than the first guess held: once more, with room for all
+        if rc in (OK, ETRUNC):
+            self.explore_total = int(n.value)
+            self.explore_sources_result = (outs[:min(n.value, want)], per, tot.as_dict())
+        _check(rc, "dash_explore_sources", self.h)
+        return self.explore_sources_result
 
     def run(self) -> dict:
         st = Stats()
