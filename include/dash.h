@@ -479,6 +479,67 @@ int dash_explore_sources(dash_t *h, uint64_t num_sources, uint64_t first_seed, u
                          const uint64_t *weights, uint64_t table_slots, dash_outcome_ex *out, uint64_t cap,
                          uint64_t *n, dash_source_summary *per_source /* [num_sources] or NULL */,
                          dash_explore_totals *totals /* or NULL */);
+
+/* ---- shrinking one system to a minimal reproducer (csrc/dash_shrink.hip) ----
+   dash_check_coherence and the explores say that a system ends in a broken state, in 16 bytes.
+   dash_shrink cuts the system down to a few instructions that still end in such a state: round by
+   round it deletes the largest block of instructions of one node that keeps the goal true, until no
+   single instruction can be deleted. Every variant of a round is written, simulated, checked and
+   ranked on the device; the host reads 8 bytes per round. The rule, stated once:
+
+   The base is a trace set with lens[t] instructions on node t < num_procs.
+
+   Candidates of a round, in the order of their index c = 0, 1, ...: by node t ascending; for each node
+   with lens[t] > 0 by level j = J, J - 1, ..., 0, where J is the least integer with 2^J >= lens[t];
+   within a level by block start s = 0, 2^j, 2 * 2^j, ... < lens[t]. The candidate deletes instructions
+   [s, min(s + 2^j, lens[t])) of node t: later instructions of that node move down, the other nodes are
+   untouched, and words at or past the new length are 0. A node of length L so has the sum over j <= J of
+   ceil(L / 2^j) candidates; C is the sum over the nodes. Level 0 holds every single deletion.
+
+   A candidate passes when its run, under the same schedule as the base, ends with
+     (coh.bits & goal.coh_all) == goal.coh_all  and
+     (errors & goal.err_all) == goal.err_all    and  (errors & goal.err_none) == 0,
+   coh being the dash_coherence record of its final state and errors its DASH_ERR_* bits.
+
+   The winner of a round is the passing candidate that deletes the most instructions; among equals, the
+   one with the lowest index. It becomes the new base. When no candidate passes the call ends: the base is
+   then 1-minimal, deleting any one instruction breaks the goal.
+
+   dash_shrink_candidate is the enumeration as pure host code (the device uses the same arithmetic,
+   shrink_decode in csrc/dash_shrink.h): it returns C for lens[0 .. num_procs), and for c < C sets *node, *start and
+   *count (each optional) to candidate c's. DASH_EINVAL for c >= C when C > 0 (with C == 0 it returns 0
+   whatever c is), for lens == NULL, num_procs outside 1..8 or a length above 2^24. */
+typedef struct dash_shrink_goal { uint32_t coh_all, err_all, err_none, _reserved; } dash_shrink_goal;
+typedef struct dash_shrink_step { uint32_t node, start, count, candidates; } dash_shrink_step; /* one per round:
+                                       the winner, and the C of the base it was taken from */
+typedef struct dash_shrink_report {
+    uint64_t rounds, passes, variants;          /* winners applied; dash_run calls (the check of the source
+                                                   and the final run included); counted candidates run */
+    uint64_t instr_before, instr_after;
+    double sim_ms, gen_ms, select_ms;           /* device events: dash_run's kernels; the candidate and apply
+                                                   kernels; the coherence launch and the select kernel */
+} dash_shrink_report;
+/* Shrinks system src of the loaded batch under the goal. seed == 0: the lockstep schedule (on a handle
+   created without schedule_seed the plain lockstep kernel; on a seeded handle every system gets seed 0);
+   seed != 0: every variant runs the seeded round schedule `seed`, as dash_set_system_seeds gives it
+   (needs a handle created with schedule_seed != 0). A round takes ceil(C / cfg.num_systems) sub-passes:
+   in sub-pass p system k holds candidate p * num_systems + k; systems past the last candidate repeat the
+   base and are not counted.
+   Results: the minimal set into packed_out[node * stride ..] (optional; the rest of a row is zeroed) and
+   lens_out[node] (optional); the rounds' winners into steps[0 .. cap), their number into *n, which may
+   exceed cap (n may be NULL when cap == 0); *report (optional). Afterwards every system of the handle
+   holds the minimal set and has run it once more, with its coherence records in place: dash_read_state,
+   dash_dump_system, dash_read_coherence and dash_read_traces work on it; on a seeded handle the seeds stay
+   set.
+   DASH_ESTATE: created without DASH_KEEP_STATE, no traces loaded, the handle follows a micro-step table,
+   seed != 0 on a handle created with schedule_seed == 0. DASH_EINVAL: src out of range, goal NULL or
+   coh_all == 0 && err_all == 0, packed_out with a stride below the source's longest trace, n == NULL
+   with cap != 0, steps == NULL with cap != 0, and a source that does not itself meet the goal
+   (dash_last_error says so, with the source's bits; the batch then holds copies of the source, run and
+   checked). */
+int dash_shrink(dash_t *h, uint64_t src, uint64_t seed, const dash_shrink_goal *goal,
+                uint16_t *packed_out /* [num_procs][stride] or NULL */, uint64_t stride, uint32_t *lens_out,
+                dash_shrink_step *steps, uint32_t cap, uint32_t *n, dash_shrink_report *report);
 /* HIP stream the engine launches on (hipStream_t as void*) */
 void *dash_stream(dash_t *h);
 
@@ -524,6 +585,17 @@ int dash_seed_schedule(uint64_t seed, uint32_t num_procs, uint32_t rounds, uint8
    DASH_EINVAL outside these ranges. Pure host code. */
 int dash_explore_assign(uint64_t S, uint64_t G, uint64_t K, uint64_t F, uint64_t pass, uint64_t k,
                         uint32_t *source, uint64_t *seed, int *counted);
+/* Candidate c of a dash_shrink round over a base of lens[0 .. num_procs) (the rule is stated with
+   dash_shrink, above). Returns C >= 0, or DASH_EINVAL. Pure host code. */
+int dash_shrink_candidate(const uint32_t *lens, uint32_t num_procs, uint64_t c,
+                          uint32_t *node, uint32_t *start, uint32_t *count);
+/* One trace set as a trace directory: out_dir/core_<n>.txt for n < num_procs (out_dir is created if
+   missing), node n's lens[n] words of packed[n * stride ..] as the fixtures write them, "RD 0x3C" and
+   "WR 0x00 110", one per line. dash_parse_core_file reads back the same words (an RD's value bits are
+   not written: they mean nothing). DASH_EINVAL for a length above stride, DASH_EIO when a file cannot
+   be written. */
+int dash_write_dir(const uint16_t *packed, uint64_t stride, const uint32_t *lens, uint32_t num_procs,
+                   const char *out_dir);
 /* initializeProcessor's parse (ref :822-850): up to max_instr records into out[]. */
 int dash_parse_core_file(const char *path, uint32_t num_procs, uint32_t max_instr,
                          uint16_t *out, uint32_t *len);

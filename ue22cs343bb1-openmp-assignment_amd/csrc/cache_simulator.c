@@ -53,6 +53,14 @@
  *       S0 + K - 1 (S0 = --micro-seed, default 0) under one weight vector (dash_explore_micro);
  *       same output lines (`--micro-seed <seed> --weights ...` then writes that state's dumps):
  *       e.g. `test_4 --explore-micro 250 --weights 4,0,31,1` lists the accepted run_3
+ *   --shrink OUTDIR [--shrink-bits 0xBB]  cut the directory's traces down, on the GPU, to a few instructions
+ *       that still end in the same broken state (dash_shrink): per round the largest block of one node's
+ *       instructions whose deletion keeps the goal, until no single instruction can go. The goal: the final
+ *       state has the coherence bits 0xBB (default: the lowest bit of the directory's own record) and no
+ *       error bit the directory's own run does not have; the schedule is lockstep or --schedule S. Prints
+ *       one line "shrink node= start= count= candidates=" per round and a last line "shrunk
+ *       instr=<before>-><after> rounds= variants= bits=0x..", writes OUTDIR/core_<n>.txt and no dumps; a
+ *       coherent directory prints "shrink: nothing to shrink (coherent)" and writes nothing
  *   --sources FILE    with --explore / --explore-micro: several trace directories in one call
  *       (dash_explore_sources). <test_directory> is source 0, FILE lists the others, one per line; K
  *       schedules of every source run side by side in the batch and their outcomes are merged and
@@ -412,6 +420,84 @@ static int explore_dir(const char *dir, unsigned n, unsigned cs, unsigned m, int
     return rc;
 }
 
+/* --shrink OUTDIR: the directory's trace set cut down on the GPU (dash_shrink) to a 1-minimal one whose
+   final state still has the coherence bits `bits` (0: the lowest bit of the source's own record) and no
+   error bit the source does not have; written to OUTDIR as core_<n>.txt */
+static int shrink_dir(const char *dir, unsigned n, unsigned cs, unsigned m, int dev, unsigned long long sched,
+                      uint32_t bits, const char *out_dir) {
+    char base[4096], path[4200];
+    int rc = dash_resolve_dir(dir, base, sizeof base);
+    if (rc != DASH_OK || n < 1 || n > DASH_MAX_PROCS) {
+        fprintf(stderr, "Error: could not open %s/core_0.txt\n", base);
+        return rc != DASH_OK ? rc : DASH_EINVAL;
+    }
+    const size_t stride = m ? m : 1, row = (size_t)n * stride;
+    uint16_t *one = (uint16_t *)calloc(2 * row, sizeof *one); /* the source, then the result */
+    uint32_t lens[2 * DASH_MAX_PROCS] = {0};
+    if (!one) return DASH_ENOMEM;
+    for (unsigned t = 0; rc == DASH_OK && t < n; t++) {
+        snprintf(path, sizeof path, "%s/core_%u.txt", base, t);
+        rc = dash_parse_core_file(path, n, m, one + t * stride, &lens[t]);
+    }
+    /* one system per candidate of the first round, up to 65,536 and to 64 MB of zeroed rows: only system
+       0's are filled on the host (dash_shrink writes the others on the device) */
+    uint64_t nsys = 1, instr = 0;
+    if (rc == DASH_OK) {
+        const int C = dash_shrink_candidate(lens, n, 0, NULL, NULL, NULL);
+        nsys = C > 65536 ? 65536 : C > 0 ? (uint64_t)C : 1;
+        if (nsys > (64u << 20) / (row * 2)) nsys = (64u << 20) / (row * 2) ? (64u << 20) / (row * 2) : 1;
+        for (unsigned t = 0; t < n; t++) instr += lens[t];
+    }
+    uint16_t *tr = (uint16_t *)calloc(nsys * row, sizeof *tr);
+    uint32_t *all_lens = (uint32_t *)calloc(nsys * n, sizeof *all_lens);
+    dash_shrink_step *steps = (dash_shrink_step *)malloc((instr ? instr : 1) * sizeof *steps);
+    dash_t *h = NULL;
+    dash_cfg cfg = {0};
+    cfg.num_procs = n;
+    cfg.cache_size = cs;
+    cfg.max_instr = m;
+    cfg.num_systems = nsys;
+    cfg.device = dev;
+    cfg.schedule_seed = sched;
+    cfg.flags = DASH_KEEP_STATE;
+    if (rc == DASH_OK && (!tr || !all_lens || !steps)) rc = DASH_ENOMEM;
+    if (rc == DASH_OK) {
+        memcpy(tr, one, row * sizeof *tr);
+        memcpy(all_lens, lens, n * sizeof *all_lens);
+    }
+    dash_coherence c = {0};
+    uint32_t errors = 0, rounds = 0;
+    if (rc == DASH_OK && (rc = dash_create(&cfg, &h)) == DASH_OK &&
+        (rc = dash_load_traces(h, tr, stride, all_lens, nsys)) == DASH_OK && (rc = dash_run(h, NULL)) == DASH_OK &&
+        (rc = dash_check_coherence(h, NULL)) == DASH_OK && (rc = dash_read_coherence(h, 0, 1, &c)) == DASH_OK)
+        rc = dash_read_results(h, 0, 1, NULL, NULL, &errors);
+    if (rc == DASH_OK && c.bits == 0 && bits == 0) {
+        printf("shrink: nothing to shrink (coherent)\n");
+    } else if (rc == DASH_OK) {
+        dash_shrink_goal goal = {bits ? bits : c.bits & (0u - c.bits), 0, ~errors, 0};
+        dash_shrink_report rep;
+        rc = dash_shrink(h, 0, sched, &goal, one + row, stride, lens + DASH_MAX_PROCS, steps, (uint32_t)instr, &rounds, &rep);
+        if (rc == DASH_OK) rc = dash_write_dir(one + row, stride, lens + DASH_MAX_PROCS, n, out_dir);
+        if (rc == DASH_OK) {
+            for (uint32_t r = 0; r < rounds; r++)
+                printf("shrink node=%u start=%u count=%u candidates=%u\n", steps[r].node, steps[r].start,
+                       steps[r].count, steps[r].candidates);
+            printf("shrunk instr=%llu->%llu rounds=%llu variants=%llu bits=0x%X\n",
+                   (unsigned long long)rep.instr_before, (unsigned long long)rep.instr_after,
+                   (unsigned long long)rep.rounds, (unsigned long long)rep.variants, goal.coh_all);
+        } else if (rc == DASH_EIO) {
+            fprintf(stderr, "cache_simulator: could not write %s\n", out_dir);
+        }
+    }
+    if (rc != DASH_OK && h) fprintf(stderr, "%s\n", dash_last_error(h));
+    dash_destroy(h);
+    free(steps);
+    free(all_lens);
+    free(tr);
+    free(one);
+    return rc;
+}
+
 /* --explore K / --explore-micro K with --sources FILE: the outcomes of several trace directories in one
    call (dash_explore_sources). dir is source 0; FILE lists the others, one per line. */
 static int explore_sources_dirs(const char *dir, const char *list, unsigned n, unsigned cs, unsigned m, int dev,
@@ -628,7 +714,8 @@ int main(int argc, char *argv[]) {
     int dev = 0, show = 0, dbg_instr = 0, dbg_msg = 0, n_given = 0, device_ingest = 0;
     const char *out = ".", *dir = NULL, *batch = NULL, *digests = NULL, *dump = NULL, *rounds_file = NULL,
                *micro_file = NULL, *write_rounds_file = NULL, *write_micro_file = NULL, *weights_text = NULL,
-               *sources_file = NULL;
+               *sources_file = NULL, *shrink_out = NULL;
+    uint32_t shrink_bits = 0;
     unsigned long long synth = 0, seed = 0x5EED, sched = 0, explore = 0, micro_seed = 0;
     int explore_given = 0, explore_micro = 0, micro_seed_given = 0, metrics = 0, coherence = 0;
     uint64_t weights = DASH_MICRO_UNIFORM;
@@ -663,6 +750,8 @@ int main(int argc, char *argv[]) {
         else if (!strcmp(argv[i], "--weights") && i + 1 < argc) weights_text = argv[++i];
         else if (!strcmp(argv[i], "--sources") && i + 1 < argc) sources_file = argv[++i];
         else if (!strcmp(argv[i], "--write-micro") && i + 1 < argc) write_micro_file = argv[++i];
+        else if (!strcmp(argv[i], "--shrink") && i + 1 < argc) shrink_out = argv[++i];
+        else if (!strcmp(argv[i], "--shrink-bits") && i + 1 < argc) shrink_bits = (uint32_t)strtoul(argv[++i], NULL, 0);
         else if (!strcmp(argv[i], "--locality") && i + 1 < argc) loc = atof(argv[++i]);
         else if (!strcmp(argv[i], "--kind") && i + 1 < argc) {
             const char *k = argv[++i];
@@ -683,6 +772,7 @@ int main(int argc, char *argv[]) {
         fprintf(stderr, "Usage: %s <test_directory>\n", argv[0]); /* ref :128 */
         fprintf(stderr, "       %s <test_directory> --metrics   per-node miss, invalidation and wait metrics\n", argv[0]);
         fprintf(stderr, "       %s <test_directory> --coherence   coherence invariants of the final state\n", argv[0]);
+        fprintf(stderr, "       %s <test_directory> --shrink OUTDIR   a minimal trace set with the same broken state\n", argv[0]);
         return EXIT_FAILURE;
     }
     if (weights_text && parse_weights(weights_text, n, &weights) != 0) {
@@ -696,6 +786,23 @@ int main(int argc, char *argv[]) {
     if (sources_file && !explore_given) {
         fprintf(stderr, "cache_simulator: --sources goes with --explore or --explore-micro\n");
         return EXIT_FAILURE;
+    }
+    if (shrink_bits && !shrink_out) {
+        fprintf(stderr, "cache_simulator: --shrink-bits goes with --shrink\n");
+        return EXIT_FAILURE;
+    }
+    if (shrink_out) {
+        if (explore_given || rounds_file || micro_file || micro_seed_given || write_rounds_file || write_micro_file ||
+            metrics || coherence) {
+            fprintf(stderr, "cache_simulator: --shrink goes with --schedule and --shrink-bits only\n");
+            return EXIT_FAILURE;
+        }
+        int rc = shrink_dir(dir, n, cs, m, dev, sched, shrink_bits, shrink_out);
+        if (rc != DASH_OK) {
+            const char *why = dash_last_error(NULL);
+            fprintf(stderr, "cache_simulator: %s (%d)\n", why[0] ? why : "failed", rc);
+        }
+        return rc == DASH_OK ? EXIT_SUCCESS : EXIT_FAILURE;
     }
     if (explore_given) {
         if (rounds_file || micro_file || write_rounds_file || write_micro_file || metrics) {

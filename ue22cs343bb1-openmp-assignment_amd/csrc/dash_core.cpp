@@ -31,6 +31,8 @@ static void release(dash_t* h) {
             if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->oc_ev)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : h->sh_ev)
+        if (e) (void)hipEventDestroy(e);
     if (h->side) (void)hipStreamSynchronize(h->side);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);

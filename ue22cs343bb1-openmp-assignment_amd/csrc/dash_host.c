@@ -99,6 +99,28 @@ int dash_parse_core_file(const char *path, uint32_t num_procs, uint32_t max_inst
     return rc;
 }
 
+/* The inverse of dash_parse_core_file for a whole trace set, in the fixtures' own spelling. */
+int dash_write_dir(const uint16_t *packed, uint64_t stride, const uint32_t *lens, uint32_t num_procs,
+                   const char *out_dir) {
+    if (!lens || !out_dir || num_procs < 1 || num_procs > DASH_MAX_PROCS) return DASH_EINVAL;
+    for (uint32_t t = 0; t < num_procs; t++)
+        if (lens[t] > stride || (lens[t] && !packed)) return DASH_EINVAL;
+    if (mkdir(out_dir, 0777) != 0 && errno != EEXIST) return DASH_EIO;
+    for (uint32_t t = 0; t < num_procs; t++) {
+        char path[4200];
+        if ((size_t)snprintf(path, sizeof path, "%s/core_%u.txt", out_dir, t) >= sizeof path) return DASH_EINVAL;
+        FILE *f = fopen(path, "w");
+        if (!f) return DASH_EIO;
+        int bad = 0;
+        for (uint32_t i = 0; i < lens[t]; i++) {
+            const unsigned w = packed[t * stride + i], addr = (w >> 8) & 0x7Fu;
+            bad |= ((w & 0x8000u) ? fprintf(f, "WR 0x%02X %u\n", addr, w & 0xFFu) : fprintf(f, "RD 0x%02X\n", addr)) < 0;
+        }
+        if (fclose(f) != 0 || bad) return DASH_EIO;
+    }
+    return DASH_OK;
+}
+
 void dash_init_node_state(dash_node_state *s, uint32_t node_id, uint32_t cache_size) {
     memset(s, 0, sizeof *s);
     for (uint32_t i = 0; i < DASH_MEM_SIZE; i++) {

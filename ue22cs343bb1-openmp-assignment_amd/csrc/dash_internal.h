@@ -1,7 +1,7 @@
 // dash_internal.h -- what the host files of libdash share: the handle, the error plumbing and
 // the helpers for device buffers and threads. Internal: not installed, not part of dash.h.
 // (dash_core.cpp, dash_sched.cpp, dash_load.cpp, dash_tools.cpp, dash_metrics.cpp,
-// dash_coherence.cpp, dash_outcomes.cpp)
+// dash_coherence.cpp, dash_outcomes.cpp, dash_shrink.cpp)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -39,7 +39,7 @@ struct dash_ctx {
     struct {
         void* p;
         bool pinned;
-    } owned[40] = {};
+    } owned[48] = {};
     uint2* d_trace = nullptr;
     uint32_t* d_lens = nullptr;
     uint64_t* d_digests = nullptr;
@@ -91,6 +91,13 @@ struct dash_ctx {
     unsigned long long* d_oc_counters = nullptr;  // [dash::OC_WORDS]
     hipEvent_t oc_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // around the kernels before / after
                                                                           // dash_run, and after the insert
+    // dash_shrink (dash_shrink.cpp): allocated on first use and kept
+    uint2* d_sh_base = nullptr;                  // [2] system rows: the base and the row the next one is written to
+    uint32_t* d_sh_lens = nullptr;               // [2][DASH_MAX_PROCS] their lengths
+    uint32_t* d_sh_count = nullptr;              // [num_systems] instructions each system's candidate deletes
+    unsigned long long* d_sh_cell = nullptr;     // the round's winner (dash::shrink_key), 0 = none
+    hipEvent_t sh_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // around the variant, select
+                                                                                  // and apply launches
     char msg[256] = {0};
     // device-side text ingest (dash_load_text / dash_load_dirs_device): buffers grown on first
     // use and kept, so a repeated load allocates nothing

@@ -17,6 +17,9 @@ libdash:
     Engine.explore_sources(g, s0, k) -> the outcomes of g trace sets at once, merged and classified on
                                       the GPU (counts, witnesses, coherence records; explore_assign
                                       states which system runs which source and seed)
+    Engine.shrink(src, coh_all)    -> one system cut down on the GPU to a 1-minimal trace set that still
+                                      ends with those coherence bits (shrink_candidate states the
+                                      candidates of a round; write_dir writes the result as core_<n>.txt)
     Engine.read_state(sys)         -> the nodes' processorNode state
     Engine.compute_metrics()       -> per-node miss / invalidation / wait metrics, reduced on the GPU
                                       from the event log (read_metrics returns the records)
@@ -74,7 +77,8 @@ EXPORTS = ("dash_create", "dash_destroy", "dash_last_error", "dash_load_traces",
            "dash_broadcast_system", "dash_seed_schedule", "dash_explore", "dash_micro_pick",
            "dash_set_micro_seeds", "dash_read_micro_acts", "dash_explore_micro", "dash_compute_metrics",
            "dash_read_metrics", "dash_check_states", "dash_check_coherence", "dash_read_coherence",
-           "dash_check_outcomes", "dash_explore_sources", "dash_explore_assign")
+           "dash_check_outcomes", "dash_explore_sources", "dash_explore_assign", "dash_shrink",
+           "dash_shrink_candidate", "dash_write_dir")
 TEXT_TILE = 4096  # DASH_TEXT_TILE: bytes per tile of the device text parser
 SIT_OUT = 0xFF
 MICRO_STEP, MICRO_SEND = 0, 1  # dash_set_micro_schedule actions
@@ -202,6 +206,22 @@ class ExploreTotals(ctypes.Structure):
         return d
 
 
+# dash_shrink_goal / dash_shrink_step / dash_shrink_report (dash_shrink)
+class ShrinkGoal(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint32) for f in ("coh_all", "err_all", "err_none", "_reserved")]
+
+
+SHRINK_STEP_DTYPE = np.dtype([(f, np.uint32) for f in ("node", "start", "count", "candidates")])
+
+
+class ShrinkReport(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint64) for f in ("rounds", "passes", "variants", "instr_before", "instr_after")] + \
+               [(f, ctypes.c_double) for f in ("sim_ms", "gen_ms", "select_ms")]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class Gen(ctypes.Structure):
     _fields_ = [("seed", ctypes.c_uint64), ("sys_base", ctypes.c_uint64), ("kind", ctypes.c_uint32),
                 ("locality", ctypes.c_uint32), ("len", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
@@ -278,6 +298,10 @@ def lib() -> ctypes.CDLL:
                                        ctypes.POINTER(ExploreTotals)]),
         "dash_explore_assign": (i32, [u64, u64, u64, u64, u64, u64, ctypes.POINTER(u32), ctypes.POINTER(u64),
                                       ctypes.POINTER(i32)]),
+        "dash_shrink": (i32, [vp, u64, u64, ctypes.POINTER(ShrinkGoal), vp, u64, vp, vp, u32, ctypes.POINTER(u32),
+                              ctypes.POINTER(ShrinkReport)]),
+        "dash_shrink_candidate": (i32, [vp, u32, u64, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32)]),
+        "dash_write_dir": (i32, [vp, u64, vp, u32, ctypes.c_char_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -443,6 +467,31 @@ def explore_assign(S: int, G: int, K: int, F: int, pass_: int, k: int):
     _check(lib().dash_explore_assign(S, G, K, F, pass_, k, ctypes.byref(src), ctypes.byref(seed),
                                      ctypes.byref(counted)), "dash_explore_assign")
     return src.value, seed.value, bool(counted.value)
+
+
+def shrink_candidate(lens, c: int):
+    """dash_shrink_candidate: (C, node, start, count) of candidate c of a shrink round over a base with
+    lens[t] instructions on node t: C candidates in all, and candidate c deletes instructions
+    [start, start + count) of `node`. C == 0 (an empty base) returns (0, None, None, None); c >= C > 0
+    raises DashError(EINVAL)."""
+    lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    assert lens.ndim == 1
+    node, start, count = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    C = lib().dash_shrink_candidate(lens.ctypes.data, len(lens), c, ctypes.byref(node), ctypes.byref(start),
+                                    ctypes.byref(count))
+    _check(C if C < 0 else OK, "dash_shrink_candidate")
+    return (C, node.value, start.value, count.value) if C else (0, None, None, None)
+
+
+def write_dir(trace, lens, out_dir):
+    """dash_write_dir: one trace set (trace [num_procs, stride] u16, lens [num_procs]) as
+    out_dir/core_<n>.txt in the fixtures' format; parse_core_file reads the same words back."""
+    trace = np.ascontiguousarray(trace, dtype=np.uint16)
+    lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    assert trace.ndim == 2 and lens.shape == (trace.shape[0],)
+    buf = trace if trace.size else np.zeros(1, dtype=np.uint16)
+    _check(lib().dash_write_dir(buf.ctypes.data, trace.shape[1], lens.ctypes.data, trace.shape[0],
+                                str(out_dir).encode()), f"dash_write_dir {out_dir}")
 
 
 def probe_box(device=0) -> dict:
@@ -699,6 +748,26 @@ class Engine:
             self.explore_sources_result = (outs[:min(n.value, want)], per, tot.as_dict())
         _check(rc, "dash_explore_sources", self.h)
         return self.explore_sources_result
+
+    def shrink(self, src: int, coh_all: int, err_all=0, err_none=0xFFFFFFFF, seed=0, cap=None) -> dict:
+        """dash_shrink: system src cut down, on the GPU, to a 1-minimal trace set whose final state still
+        has the coherence bits coh_all, the error bits err_all and none of err_none, under the lockstep
+        schedule (seed 0) or the seeded round schedule `seed`. Returns dict(trace [num_procs, max_instr]
+        u16, lens [num_procs], steps: one SHRINK_STEP_DTYPE record per round (the winner and the base's
+        candidate count), report dict). Afterwards every system holds the minimal set, run and checked.
+        cap=k keeps the first k steps (report["rounds"] has their number)."""
+        goal = ShrinkGoal(coh_all, err_all, err_none, 0)
+        stride = max(int(self.cfg.max_instr), 1)
+        trace = np.zeros((self.num_procs, stride), dtype=np.uint16)
+        lens = np.zeros(self.num_procs, dtype=np.uint32)
+        # every round deletes at least one instruction, so a source has at most as many rounds as
+        # instructions (the call cannot be repeated for a longer list: it leaves the minimal set behind)
+        want = min(self.num_procs * stride, 1 << 20) if cap is None else cap
+        steps = np.zeros(max(want, 1), dtype=SHRINK_STEP_DTYPE)
+        n, rep = ctypes.c_uint32(), ShrinkReport()
+        _check(lib().dash_shrink(self.h, src, seed, ctypes.byref(goal), trace.ctypes.data, stride, lens.ctypes.data,
+                                 steps.ctypes.data, want, ctypes.byref(n), ctypes.byref(rep)), "dash_shrink", self.h)
+        return {"trace": trace, "lens": lens, "steps": steps[:min(n.value, want)], "report": rep.as_dict()}
 
     def run(self) -> dict:
         st = Stats()
