@@ -352,53 +352,108 @@ static int write_rounds(const char *path, unsigned long long sched, unsigned n, 
     return rc;
 }
 
-/* --explore K / --explore-micro K (weights != NULL): the distinct outcomes of K seeded schedules of one
-   trace directory */
-static int explore_dir(const char *dir, unsigned n, unsigned cs, unsigned m, int dev, unsigned long long k,
-                       unsigned long long s0, const uint64_t *weights, int coherence) {
+/* The batch of a search call (--explore, --shrink): only the sources' rows are filled on the host, the
+   call writes the other systems on the device. */
+typedef struct {
+    uint16_t *tr;   /* [nsys][n][stride], zero but for the sources */
+    uint32_t *lens; /* [nsys][n] */
+    size_t stride;
+    uint64_t nsys;
+} batch;
+
+static void batch_free(batch *b) {
+    free(b->tr);
+    free(b->lens);
+}
+
+/* The trace sets of dirs[0 .. g) as systems 0 .. g-1 of a batch of g systems; a directory that cannot be
+   resolved is named on stderr. */
+static int batch_parse(batch *b, const char *const *dirs, size_t g, unsigned n, unsigned m) {
     char base[4096], path[4200];
-    int rc = dash_resolve_dir(dir, base, sizeof base);
-    if (rc != DASH_OK || n < 1 || n > DASH_MAX_PROCS) {
-        fprintf(stderr, "Error: could not open %s/core_0.txt\n", base);
-        return rc != DASH_OK ? rc : DASH_EINVAL;
+    int rc = DASH_OK;
+    b->stride = m ? m : 1;
+    b->nsys = g;
+    for (size_t s = 0; rc == DASH_OK && s < g; s++) {
+        rc = dash_resolve_dir(dirs[s], base, sizeof base);
+        if (rc != DASH_OK || n < 1 || n > DASH_MAX_PROCS) {
+            fprintf(stderr, "Error: could not open %s/core_0.txt\n", base);
+            return rc != DASH_OK ? rc : DASH_EINVAL;
+        }
+        if (!b->tr) {
+            b->tr = (uint16_t *)calloc(g * n * b->stride, sizeof *b->tr);
+            b->lens = (uint32_t *)calloc(g * n, sizeof *b->lens);
+            if (!b->tr || !b->lens) return DASH_ENOMEM;
+        }
+        for (unsigned t = 0; rc == DASH_OK && t < n; t++) {
+            snprintf(path, sizeof path, "%s/core_%u.txt", base, t);
+            rc = dash_parse_core_file(path, n, m, b->tr + (s * n + t) * b->stride, &b->lens[s * n + t]);
+        }
     }
-    /* one batch holds up to 65,536 schedules; only system 0's rows are filled on the host (the
-       others are empty until dash_explore copies system 0 over them on the device), and the
-       zeroed buffer stays below 64 MB whatever -m says */
-    const size_t stride = m ? m : 1, row = (size_t)n * stride;
-    uint64_t nsys = k < 65536 ? (k ? k : 1) : 65536;
-    if (nsys > (64u << 20) / (row * 2)) nsys = (64u << 20) / (row * 2) ? (64u << 20) / (row * 2) : 1;
-    uint16_t *tr = (uint16_t *)calloc(nsys * row, sizeof *tr);
-    uint32_t *lens = (uint32_t *)calloc(nsys * n, sizeof *lens);
-    dash_t *h = NULL;
+    return rc;
+}
+
+/* The batch grown to `want` systems, of at most 65,536 and of fewer where its zeroed rows would pass
+   64 MB, but never below its sources: the new systems are empty. */
+static int batch_grow(batch *b, uint64_t want, unsigned n) {
+    const size_t row = (size_t)n * b->stride;
+    const uint64_t g = b->nsys;
+    uint64_t nsys = want < 65536 ? want : 65536;
+    if (nsys > (64u << 20) / (row * 2)) nsys = (64u << 20) / (row * 2);
+    if (nsys < g) nsys = g;
+    uint16_t *tr = (uint16_t *)realloc(b->tr, nsys * row * sizeof *tr);
+    if (tr) b->tr = tr;
+    uint32_t *lens = (uint32_t *)realloc(b->lens, nsys * n * sizeof *lens);
+    if (lens) b->lens = lens;
+    if (!tr || !lens) return DASH_ENOMEM;
+    memset(tr + g * row, 0, (nsys - g) * row * sizeof *tr);
+    memset(lens + g * n, 0, (nsys - g) * n * sizeof *lens);
+    b->nsys = nsys;
+    return DASH_OK;
+}
+
+/* a handle of the batch's size, loaded with it; *h stays NULL where it could not be created */
+static int batch_handle(const batch *b, unsigned n, unsigned cs, unsigned m, int dev, unsigned long long sched,
+                        uint32_t flags, dash_t **h) {
     dash_cfg cfg = {0};
     cfg.num_procs = n;
     cfg.cache_size = cs;
     cfg.max_instr = m;
-    cfg.num_systems = nsys;
+    cfg.num_systems = b->nsys;
     cfg.device = dev;
-    cfg.schedule_seed = 1; /* any seeded handle: every system gets a seed of its own */
-    cfg.flags = coherence ? DASH_KEEP_STATE : 0; /* the final states stay on the device for the check */
-    if (!tr || !lens) rc = DASH_ENOMEM;
-    for (unsigned t = 0; rc == DASH_OK && t < n; t++) {
-        snprintf(path, sizeof path, "%s/core_%u.txt", base, t);
-        rc = dash_parse_core_file(path, n, m, tr + t * stride, &lens[t]);
+    cfg.schedule_seed = sched;
+    cfg.flags = flags;
+    const int rc = dash_create(&cfg, h);
+    return rc == DASH_OK ? dash_load_traces(*h, b->tr, b->stride, b->lens, b->nsys) : rc;
+}
+
+/* rc = CALL, which fills o[0 .. cap) and sets total, with room for `cap` entries and, in the rare case
+   that there are more, once more with room for all of them */
+#define CALL_WITH_ROOM(rc, o, cap, total, CALL)            \
+    for (int again_ = 0; again_ < 2; again_++) {           \
+        free(o);                                           \
+        (o) = malloc((size_t)(cap) * sizeof *(o));         \
+        (rc) = (o) ? (CALL) : DASH_ENOMEM;                 \
+        if ((rc) != DASH_OK || (total) <= (cap)) break;    \
+        (cap) = (total);                                   \
     }
-    if (rc == DASH_OK && (rc = dash_create(&cfg, &h)) == DASH_OK &&
-        (rc = dash_load_traces(h, tr, stride, lens, nsys)) == DASH_OK) {
+
+/* --explore K / --explore-micro K (weights != NULL): the distinct outcomes of K seeded schedules of one
+   trace directory */
+static int explore_dir(const char *dir, unsigned n, unsigned cs, unsigned m, int dev, unsigned long long k,
+                       unsigned long long s0, const uint64_t *weights, int coherence) {
+    batch b = {0};
+    dash_t *h = NULL;
+    /* one batch holds up to 65,536 schedules; any seeded handle: every system gets a seed of its own; with
+       --coherence the final states stay on the device for the check */
+    int rc = batch_parse(&b, (const char *const *)&dir, 1, n, m);
+    if (rc == DASH_OK) rc = batch_grow(&b, k ? k : 1, n);
+    if (rc == DASH_OK) rc = batch_handle(&b, n, cs, m, dev, 1, coherence ? DASH_KEEP_STATE : 0, &h);
+    if (rc == DASH_OK) {
         uint32_t total = 0, cap = 256;
-        dash_outcome *o = (dash_outcome *)malloc(cap * sizeof *o);
-        if (!o) rc = DASH_ENOMEM;
-        else rc = weights ? dash_explore_micro(h, 0, s0, k, *weights, o, cap, &total)
-                          : dash_explore(h, 0, s0, k, o, cap, &total);
-        if (rc == DASH_OK && total > cap) { /* rare: once more, with room for all of them */
-            cap = total;
-            free(o);
-            o = (dash_outcome *)malloc((size_t)cap * sizeof *o);
-            rc = !o ? DASH_ENOMEM
-                 : weights ? dash_explore_micro(h, 0, s0, k, *weights, o, cap, &total)
-                           : dash_explore(h, 0, s0, k, o, cap, &total);
-        }
+        dash_outcome *o = NULL;
+        CALL_WITH_ROOM(rc, o, cap, total,
+                       weights ? dash_explore_micro(h, 0, s0, k, *weights, o, cap, &total)
+                               : dash_explore(h, 0, s0, k, o, cap, &total));
         dash_coherence *c = NULL;
         if (rc == DASH_OK && coherence) {
             c = (dash_coherence *)malloc((total ? total : 1) * sizeof *c);
@@ -415,8 +470,7 @@ static int explore_dir(const char *dir, unsigned n, unsigned cs, unsigned m, int
     }
     if (rc != DASH_OK && h) fprintf(stderr, "%s\n", dash_last_error(h));
     dash_destroy(h);
-    free(tr);
-    free(lens);
+    batch_free(&b);
     return rc;
 }
 
@@ -425,59 +479,32 @@ static int explore_dir(const char *dir, unsigned n, unsigned cs, unsigned m, int
    error bit the source does not have; written to OUTDIR as core_<n>.txt */
 static int shrink_dir(const char *dir, unsigned n, unsigned cs, unsigned m, int dev, unsigned long long sched,
                       uint32_t bits, const char *out_dir) {
-    char base[4096], path[4200];
-    int rc = dash_resolve_dir(dir, base, sizeof base);
-    if (rc != DASH_OK || n < 1 || n > DASH_MAX_PROCS) {
-        fprintf(stderr, "Error: could not open %s/core_0.txt\n", base);
-        return rc != DASH_OK ? rc : DASH_EINVAL;
-    }
-    const size_t stride = m ? m : 1, row = (size_t)n * stride;
-    uint16_t *one = (uint16_t *)calloc(2 * row, sizeof *one); /* the source, then the result */
-    uint32_t lens[2 * DASH_MAX_PROCS] = {0};
-    if (!one) return DASH_ENOMEM;
-    for (unsigned t = 0; rc == DASH_OK && t < n; t++) {
-        snprintf(path, sizeof path, "%s/core_%u.txt", base, t);
-        rc = dash_parse_core_file(path, n, m, one + t * stride, &lens[t]);
-    }
-    /* one system per candidate of the first round, up to 65,536 and to 64 MB of zeroed rows: only system
-       0's are filled on the host (dash_shrink writes the others on the device) */
-    uint64_t nsys = 1, instr = 0;
-    if (rc == DASH_OK) {
-        const int C = dash_shrink_candidate(lens, n, 0, NULL, NULL, NULL);
-        nsys = C > 65536 ? 65536 : C > 0 ? (uint64_t)C : 1;
-        if (nsys > (64u << 20) / (row * 2)) nsys = (64u << 20) / (row * 2) ? (64u << 20) / (row * 2) : 1;
-        for (unsigned t = 0; t < n; t++) instr += lens[t];
-    }
-    uint16_t *tr = (uint16_t *)calloc(nsys * row, sizeof *tr);
-    uint32_t *all_lens = (uint32_t *)calloc(nsys * n, sizeof *all_lens);
-    dash_shrink_step *steps = (dash_shrink_step *)malloc((instr ? instr : 1) * sizeof *steps);
+    batch b = {0};
     dash_t *h = NULL;
-    dash_cfg cfg = {0};
-    cfg.num_procs = n;
-    cfg.cache_size = cs;
-    cfg.max_instr = m;
-    cfg.num_systems = nsys;
-    cfg.device = dev;
-    cfg.schedule_seed = sched;
-    cfg.flags = DASH_KEEP_STATE;
-    if (rc == DASH_OK && (!tr || !all_lens || !steps)) rc = DASH_ENOMEM;
-    if (rc == DASH_OK) {
-        memcpy(tr, one, row * sizeof *tr);
-        memcpy(all_lens, lens, n * sizeof *all_lens);
+    uint64_t instr = 0;
+    int rc = batch_parse(&b, (const char *const *)&dir, 1, n, m);
+    if (rc == DASH_OK) { /* one system per candidate of the first round */
+        const int C = dash_shrink_candidate(b.lens, n, 0, NULL, NULL, NULL);
+        for (unsigned t = 0; t < n; t++) instr += b.lens[t];
+        rc = batch_grow(&b, C > 0 ? (uint64_t)C : 1, n);
     }
+    uint16_t *min_tr = (uint16_t *)calloc((size_t)n * b.stride, sizeof *min_tr); /* the result */
+    uint32_t min_lens[DASH_MAX_PROCS] = {0};
+    dash_shrink_step *steps = (dash_shrink_step *)malloc((instr ? instr : 1) * sizeof *steps);
+    if (rc == DASH_OK && (!min_tr || !steps)) rc = DASH_ENOMEM;
     dash_coherence c = {0};
     uint32_t errors = 0, rounds = 0;
-    if (rc == DASH_OK && (rc = dash_create(&cfg, &h)) == DASH_OK &&
-        (rc = dash_load_traces(h, tr, stride, all_lens, nsys)) == DASH_OK && (rc = dash_run(h, NULL)) == DASH_OK &&
-        (rc = dash_check_coherence(h, NULL)) == DASH_OK && (rc = dash_read_coherence(h, 0, 1, &c)) == DASH_OK)
+    if (rc == DASH_OK && (rc = batch_handle(&b, n, cs, m, dev, sched, DASH_KEEP_STATE, &h)) == DASH_OK &&
+        (rc = dash_run(h, NULL)) == DASH_OK && (rc = dash_check_coherence(h, NULL)) == DASH_OK &&
+        (rc = dash_read_coherence(h, 0, 1, &c)) == DASH_OK)
         rc = dash_read_results(h, 0, 1, NULL, NULL, &errors);
     if (rc == DASH_OK && c.bits == 0 && bits == 0) {
         printf("shrink: nothing to shrink (coherent)\n");
     } else if (rc == DASH_OK) {
         dash_shrink_goal goal = {bits ? bits : c.bits & (0u - c.bits), 0, ~errors, 0};
         dash_shrink_report rep;
-        rc = dash_shrink(h, 0, sched, &goal, one + row, stride, lens + DASH_MAX_PROCS, steps, (uint32_t)instr, &rounds, &rep);
-        if (rc == DASH_OK) rc = dash_write_dir(one + row, stride, lens + DASH_MAX_PROCS, n, out_dir);
+        rc = dash_shrink(h, 0, sched, &goal, min_tr, b.stride, min_lens, steps, (uint32_t)instr, &rounds, &rep);
+        if (rc == DASH_OK) rc = dash_write_dir(min_tr, b.stride, min_lens, n, out_dir);
         if (rc == DASH_OK) {
             for (uint32_t r = 0; r < rounds; r++)
                 printf("shrink node=%u start=%u count=%u candidates=%u\n", steps[r].node, steps[r].start,
@@ -492,9 +519,8 @@ static int shrink_dir(const char *dir, unsigned n, unsigned cs, unsigned m, int 
     if (rc != DASH_OK && h) fprintf(stderr, "%s\n", dash_last_error(h));
     dash_destroy(h);
     free(steps);
-    free(all_lens);
-    free(tr);
-    free(one);
+    free(min_tr);
+    batch_free(&b);
     return rc;
 }
 
@@ -523,46 +549,19 @@ static int explore_sources_dirs(const char *dir, const char *list, unsigned n, u
         if (rc == DASH_OK && !(dirs[g++] = strdup(line))) rc = DASH_ENOMEM;
     }
     fclose(f);
-    /* a handle of up to 65,536 systems, at least one per source; only the sources' rows are filled on the
-       host (the call copies them over the others on the device); the buffer stays below 64 MB when the
-       sources allow it */
-    const size_t stride = m ? m : 1, row = (size_t)n * stride;
-    uint64_t nsys = k && g * k < 65536 ? g * k : 65536;
-    if (nsys > (64u << 20) / (row * 2)) nsys = (64u << 20) / (row * 2);
-    if (nsys < g) nsys = g;
-    uint16_t *tr = rc == DASH_OK ? (uint16_t *)calloc(nsys * row, sizeof *tr) : NULL;
-    uint32_t *lens = rc == DASH_OK ? (uint32_t *)calloc(nsys * n, sizeof *lens) : NULL;
-    if (rc == DASH_OK && (!tr || !lens)) rc = DASH_ENOMEM;
-    for (size_t s = 0; rc == DASH_OK && s < g; s++) {
-        char base[4096], path[4200];
-        if ((rc = dash_resolve_dir(dirs[s], base, sizeof base)) != DASH_OK)
-            fprintf(stderr, "Error: could not open %s/core_0.txt\n", base);
-        for (unsigned t = 0; rc == DASH_OK && t < n; t++) {
-            snprintf(path, sizeof path, "%s/core_%u.txt", base, t);
-            rc = dash_parse_core_file(path, n, m, tr + (s * n + t) * stride, &lens[s * n + t]);
-        }
-    }
+    /* a handle of up to 65,536 systems, at least one per source; any seeded handle: every system gets a
+       seed of its own; the outcomes are classified from the final states of the passes */
+    batch b = {0};
     dash_t *h = NULL;
-    dash_cfg cfg = {0};
-    cfg.num_procs = n;
-    cfg.cache_size = cs;
-    cfg.max_instr = m;
-    cfg.num_systems = nsys;
-    cfg.device = dev;
-    cfg.schedule_seed = 1; /* any seeded handle: every system gets a seed of its own */
-    cfg.flags = DASH_KEEP_STATE; /* the outcomes are classified from the final states of the passes */
-    if (rc == DASH_OK && (rc = dash_create(&cfg, &h)) == DASH_OK &&
-        (rc = dash_load_traces(h, tr, stride, lens, nsys)) == DASH_OK) {
+    if (rc == DASH_OK) rc = batch_parse(&b, (const char *const *)dirs, g, n, m);
+    if (rc == DASH_OK) rc = batch_grow(&b, k && g * k < 65536 ? g * k : 65536, n);
+    if (rc == DASH_OK) rc = batch_handle(&b, n, cs, m, dev, 1, DASH_KEEP_STATE, &h);
+    if (rc == DASH_OK) {
         uint64_t total = 0, cap = 4096;
-        dash_outcome_ex *o = (dash_outcome_ex *)malloc(cap * sizeof *o);
+        dash_outcome_ex *o = NULL;
         dash_source_summary *per = (dash_source_summary *)calloc(g, sizeof *per);
-        rc = o && per ? dash_explore_sources(h, g, s0, k, weights, 0, o, cap, &total, per, NULL) : DASH_ENOMEM;
-        if (rc == DASH_OK && total > cap) { /* rare: once more, with room for all of them */
-            cap = total;
-            free(o);
-            o = (dash_outcome_ex *)malloc((size_t)cap * sizeof *o);
-            rc = o ? dash_explore_sources(h, g, s0, k, weights, 0, o, cap, &total, per, NULL) : DASH_ENOMEM;
-        }
+        CALL_WITH_ROOM(rc, o, cap, total,
+                       per ? dash_explore_sources(h, g, s0, k, weights, 0, o, cap, &total, per, NULL) : DASH_ENOMEM);
         for (uint64_t i = 0; rc == DASH_OK && i < total && i < cap; i++) {
             printf("%u %016llx %llu %llu %u %x", o[i].source, (unsigned long long)o[i].o.digest,
                    (unsigned long long)o[i].o.count, (unsigned long long)o[i].o.seed, o[i].o.rounds, o[i].o.errors);
@@ -577,8 +576,7 @@ static int explore_sources_dirs(const char *dir, const char *list, unsigned n, u
     }
     if (rc != DASH_OK && h) fprintf(stderr, "%s\n", dash_last_error(h));
     dash_destroy(h);
-    free(tr);
-    free(lens);
+    batch_free(&b);
     for (size_t s = 0; dirs && s < g; s++) free(dirs[s]);
     free(dirs);
     return rc;

@@ -6,12 +6,6 @@
 // (:149-155) and the per-thread private processorNode (:145).
 #include "dash_internal.h"
 
-static uint32_t next_pow2(uint32_t n) {
-    uint32_t p = 1;
-    while (p < n) p <<= 1;
-    return p;
-}
-
 extern "C" {
 
 // largest round cap: event words carry the round in bits 30..0 (bit 31 = issued instruction)
@@ -26,12 +20,7 @@ static void release(dash_t* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (auto& o : h->owned)
         if (o.p) (void)(o.pinned ? hipHostFree(o.p) : hipFree(o.p));
-    for (auto& slab : h->iev)
-        for (hipEvent_t e : slab)
-            if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->oc_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->sh_ev)
+    for (hipEvent_t e : h->events)
         if (e) (void)hipEventDestroy(e);
     if (h->side) (void)hipStreamSynchronize(h->side);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -75,7 +64,7 @@ int dash_create(const dash_cfg* cfg, dash_t** out) {
     // clamped below 2^31 (event words keep the round in bits 30..0) before it is rounded up to
     // the multiple of 4 the kernel tests at the first round of every trip (no wrap to 0)
     h->cfg.max_rounds = (std::min<uint64_t>(h->cfg.max_rounds, MAX_ROUNDS_CAP) + 3) & ~3ull;
-    h->seg = next_pow2(N);
+    h->seg = (uint32_t)next_pow2(N);
     const uint64_t spw = 64 / h->seg;
     h->groups = (cfg->num_systems + spw - 1) / spw;
     {
@@ -197,10 +186,9 @@ int dash_load_traces(dash_t* h, const uint16_t* packed, uint64_t stride, const u
         HIPCHK(h, dash::launch_clear_rd(h->d_trace, words, h->stream));
         if (num_systems)
             HIPCHK(h, hipMemcpyAsync(h->d_lens, lens, num_systems * N * 4, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, reset_hint(h));
+        HIPCHK(h, traces_changed(h));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         h->loaded = true;
-        h->ran = false;
         return DASH_OK;
     });
 }
@@ -224,10 +212,9 @@ int dash_generate(dash_t* h, const dash_gen* g) {
     a.len = g->len;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, dash::launch_gen(a, h->stream));
-    HIPCHK(h, reset_hint(h));
+    HIPCHK(h, traces_changed(h));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->loaded = true;
-    h->ran = false;
     return DASH_OK;
 }
 
@@ -276,8 +263,8 @@ static dash::SimArgs sim_args(const dash_t* h) {
 int dash_run(dash_t* h, dash_stats* stats) {
     if (!h) return DASH_EINVAL;
     if (!h->loaded) return fail(h, DASH_ESTATE, "no traces loaded");
-    h->metrics = false;  // dash_compute_metrics' records are the previous run's
-    h->coherence = false;  // and dash_check_coherence's
+    h->met.valid = false;  // dash_compute_metrics' records are the previous run's
+    h->coh.valid = false;  // and dash_check_coherence's
     dash::SimArgs a = sim_args(h);
     const uint64_t spw = 64 / h->seg;
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -549,30 +536,23 @@ int dash_read_traces(dash_t* h, uint16_t* packed, uint64_t stride, uint32_t* len
             if (lens[r] > stride)
                 return fail(h, DASH_EINVAL, "dash_read_traces: trace %llu holds %u words, stride %llu",
                             (unsigned long long)r, lens[r], (unsigned long long)stride);
+        // system s node t is row s * N + t in both layouts
+        if (P == N) return copy_rows_out(h, h->d_trace, rows, lens, packed, stride);
         constexpr uint32_t C = dash::CHUNK_INSTR;
-        const uint64_t pitch = (uint64_t)h->nchunks * 8;  // device row stride in bytes
-        const uint64_t width = std::min<uint64_t>(stride * 2, pitch);
-        if (rows && width) {
-            if (P == N) {  // system s node t is row s * N + t in both layouts
-                HIPCHK(h, hipMemcpy2DAsync(packed, stride * 2, h->d_trace, pitch, width, rows, hipMemcpyDeviceToHost,
-                                           h->stream));
-                HIPCHK(h, hipStreamSynchronize(h->stream));
-            } else {
-                const uint64_t words = h->groups * (uint64_t)h->nchunks * 64;
-                std::vector<uint16_t> host(words * C);
-                HIPCHK(h, hipMemcpyAsync(host.data(), h->d_trace, words * 8, hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(h, hipStreamSynchronize(h->stream));
-                for (uint64_t s = 0; s < h->cfg.num_systems; s++) {
-                    const uint64_t g = s / (64 / P);
-                    const uint32_t lane0 = (uint32_t)(s % (64 / P)) * P;
-                    for (uint32_t t = 0; t < N; t++)
-                        memcpy(packed + (s * N + t) * stride, &host[(g * 64 + lane0 + t) * h->nchunks * C],
-                               (size_t)lens[s * N + t] * 2);
-                }
+        if (rows && stride && h->nchunks) {
+            const uint64_t words = h->groups * (uint64_t)h->nchunks * 64;
+            std::vector<uint16_t> host(words * C);
+            HIPCHK(h, hipMemcpyAsync(host.data(), h->d_trace, words * 8, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            for (uint64_t s = 0; s < h->cfg.num_systems; s++) {
+                const uint64_t g = s / (64 / P);
+                const uint32_t lane0 = (uint32_t)(s % (64 / P)) * P;
+                for (uint32_t t = 0; t < N; t++)
+                    memcpy(packed + (s * N + t) * stride, &host[(g * 64 + lane0 + t) * h->nchunks * C],
+                           (size_t)lens[s * N + t] * 2);
             }
         }
-        for (uint64_t r = 0; r < rows; r++)  // words at or past a row's length have no defined content
-            if (stride > lens[r]) memset(packed + r * stride + lens[r], 0, (size_t)(stride - lens[r]) * 2);
+        zero_past_lens(packed, stride, rows, lens);
         return DASH_OK;
     });
 }

@@ -2,6 +2,19 @@
 // the helpers for device buffers and threads. Internal: not installed, not part of dash.h.
 // (dash_core.cpp, dash_sched.cpp, dash_load.cpp, dash_tools.cpp, dash_metrics.cpp,
 // dash_coherence.cpp, dash_outcomes.cpp, dash_shrink.cpp)
+//
+// Four mechanisms are written here once, and a new search call is written against them:
+//  * What voids results. traces_changed and schedule_changed are the only places that mark the
+//    handle as not run, say what it follows and drop the overflow hint; every load, every
+//    dash_set_* call and every pass of a search goes through one of them.
+//  * Buffers on first use. alloc_group allocates all of a feature's buffers or none, ensure_seeds
+//    the per-system seed buffers, grow a buffer that is kept while it fits. All of it is entered
+//    into owned[], which release() frees.
+//  * Stage timing. A stage_timer's events are created on first use and entered into events[], which
+//    release() destroys; mark(i) records one, add(a, b, sum) adds the time between two.
+//  * One pass of a search. run_pass for the calls that write traces or seeds on the device
+//    (dash_explore_sources, dash_shrink): the change, dash_run, its kernel time. for_each_seed_pass
+//    for the host-driven search over seeds (dash_explore, dash_explore_micro, dash_check_outcomes).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,6 +29,24 @@
 
 #include "dash.h"
 #include "dash_device.h"
+
+namespace dash {
+struct OutcomeSlot;  // dash_outcomes.h
+struct OutcomeOut;
+}  // namespace dash
+
+// Stage timing with device events: mark(i) records event i on a stream, add(a, b, sum) adds the
+// milliseconds between two completed marks. timer_ready (below) creates the events.
+struct stage_timer {
+    hipEvent_t ev[6] = {};
+    hipError_t mark(int i, hipStream_t s) const { return hipEventRecord(ev[i], s); }
+    hipError_t add(int a, int b, double& sum) const {
+        float ms = 0.f;
+        const hipError_t e = hipEventElapsedTime(&ms, ev[a], ev[b]);
+        sum += ms;
+        return e;
+    }
+};
 
 // which schedule dash_run follows (the dash_set_* call made last decides)
 enum class sched_src : uint8_t {
@@ -40,6 +71,7 @@ struct dash_ctx {
         void* p;
         bool pinned;
     } owned[48] = {};
+    hipEvent_t events[24] = {};  // the stage timers' events: timer_ready enters them, release() destroys them
     uint2* d_trace = nullptr;
     uint32_t* d_lens = nullptr;
     uint64_t* d_digests = nullptr;
@@ -73,47 +105,51 @@ struct dash_ctx {
     int hint_tier = -1;
     bool loaded = false;
     bool ran = false;
-    // dash_compute_metrics (dash_metrics.cpp): allocated on first use; dash_run invalidates them
-    uint4* d_metrics = nullptr;                  // [num_systems * num_procs] 64-B records
-    uint8_t* d_metrics_cut = nullptr;            // [num_systems] log shorter than the run
-    unsigned long long* d_metrics_tot = nullptr;  // [dash::TOT_WORDS]
-    bool metrics = false;                        // the records are those of the last run
-    // dash_check_coherence (dash_coherence.cpp): likewise
-    uint4* d_coh = nullptr;                      // [num_systems] dash_coherence records
-    unsigned long long* d_coh_tot = nullptr;     // [dash::COH_TOT_WORDS]
-    bool coherence = false;                      // the records are those of the last run
-    // dash_explore_sources (dash_outcomes.cpp): allocated by the call, kept and reused while they fit
-    void* d_oc_table = nullptr;                  // [oc_slots] dash::OutcomeSlot
-    uint64_t oc_slots = 0;
-    void* d_oc_out = nullptr;                    // [oc_out_cap] compacted entries (dash_outcome_ex)
-    uint64_t oc_out_cap = 0;
-    uint32_t* d_oc_place = nullptr;              // [num_systems] the slot of every system of the pass
-    unsigned long long* d_oc_counters = nullptr;  // [dash::OC_WORDS]
-    hipEvent_t oc_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // around the kernels before / after
-                                                                          // dash_run, and after the insert
-    // dash_shrink (dash_shrink.cpp): allocated on first use and kept
-    uint2* d_sh_base = nullptr;                  // [2] system rows: the base and the row the next one is written to
-    uint32_t* d_sh_lens = nullptr;               // [2][DASH_MAX_PROCS] their lengths
-    uint32_t* d_sh_count = nullptr;              // [num_systems] instructions each system's candidate deletes
-    unsigned long long* d_sh_cell = nullptr;     // the round's winner (dash::shrink_key), 0 = none
-    hipEvent_t sh_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // around the variant, select
-                                                                                  // and apply launches
     char msg[256] = {0};
-    // device-side text ingest (dash_load_text / dash_load_dirs_device): buffers grown on first
-    // use and kept, so a repeated load allocates nothing
-    uint8_t* d_text = nullptr;  // text slab
-    uint64_t d_text_cap = 0;
-    uint64_t* d_foff = nullptr;  // per file of a launch: offset, length
-    uint32_t* d_flen = nullptr;
-    uint64_t d_files_cap = 0;
-    unsigned long long* d_fail = nullptr;  // first-failure cell (dash_ingest.h)
-    char* pin[2] = {nullptr, nullptr};     // pinned slabs of dash_load_dirs_device
-    uint64_t pin_cap = 0;
-    uint64_t* pin_off[2] = {nullptr, nullptr};
-    uint32_t* pin_len[2] = {nullptr, nullptr};
-    uint64_t pin_files_cap = 0;
-    hipEvent_t iev[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
-    dash_ingest_report ingest{};
+    // What follows is allocated on first use, one group per host file that owns it.
+    struct {  // dash_compute_metrics (dash_metrics.cpp); dash_run invalidates the records
+        uint4* d_rec = nullptr;                // [num_systems * num_procs] 64-B records
+        uint8_t* d_cut = nullptr;              // [num_systems] log shorter than the run
+        unsigned long long* d_tot = nullptr;   // [dash::TOT_WORDS]
+        bool valid = false;                    // the records are those of the last run
+    } met;
+    struct {  // dash_check_coherence (dash_coherence.cpp): likewise
+        uint4* d_rec = nullptr;                // [num_systems] dash_coherence records
+        unsigned long long* d_tot = nullptr;   // [dash::COH_TOT_WORDS]
+        bool valid = false;                    // the records are those of the last run
+    } coh;
+    struct {  // dash_explore_sources (dash_outcomes.cpp): kept and reused while they fit
+        dash::OutcomeSlot* d_table = nullptr;  // [slots]
+        uint64_t slots = 0;
+        dash::OutcomeOut* d_out = nullptr;     // [out_cap] compacted entries (dash_outcome_ex)
+        uint64_t out_cap = 0;
+        uint32_t* d_place = nullptr;           // [num_systems] the slot of every system of the pass
+        unsigned long long* d_counters = nullptr;  // [dash::OC_WORDS]
+        stage_timer timer;                     // 5 marks: around the kernels before / after dash_run, and after the insert
+    } oc;
+    struct {  // dash_shrink (dash_shrink.cpp)
+        uint2* d_base = nullptr;               // [2] system rows: the base and the row the next one is written to
+        uint32_t* d_lens = nullptr;            // [2][DASH_MAX_PROCS] their lengths
+        uint32_t* d_count = nullptr;           // [num_systems] instructions each system's candidate deletes
+        unsigned long long* d_cell = nullptr;  // the round's winner (dash::shrink_key), 0 = none
+        stage_timer timer;                     // 6 marks: around the variant, select and apply launches
+    } sh;
+    struct {  // device-side text ingest (dash_load.cpp): grown on first use and kept, so a repeated
+              // load allocates nothing
+        uint8_t* d_text = nullptr;  // text slab
+        uint64_t text_cap = 0;
+        uint64_t* d_foff = nullptr;  // per file of a launch: offset, length
+        uint32_t* d_flen = nullptr;
+        uint64_t files_cap = 0;
+        unsigned long long* d_fail = nullptr;  // first-failure cell (dash_ingest.h)
+        char* pin[2] = {nullptr, nullptr};     // pinned slabs of dash_load_dirs_device
+        uint64_t pin_cap = 0;
+        uint64_t* pin_off[2] = {nullptr, nullptr};
+        uint32_t* pin_len[2] = {nullptr, nullptr};
+        uint64_t pin_files_cap = 0;
+        stage_timer timer[2];  // per pinned slab, 3 marks: before its copy, after it, after its parse
+        dash_ingest_report report{};
+    } ingest;
 };
 
 inline int fail(dash_t* h, int code, const char* fmt, ...) {
@@ -163,12 +199,150 @@ hipError_t buf_alloc(dash_t* h, T*& p, uint64_t n, bool pinned = false) {
     return e;
 }
 
-// new traces: the overflow hint no longer applies
+// All of a feature's buffers or none: (pointer, elements) pairs, allocated in order; after a failure
+// those already made are freed again.
+inline hipError_t alloc_all(dash_t*) { return hipSuccess; }
+template <class T, class... Rest>
+hipError_t alloc_all(dash_t* h, T*& p, uint64_t n, Rest&&... rest) {
+    hipError_t e = buf_alloc(h, p, n);
+    if (e == hipSuccess) e = alloc_all(h, rest...);
+    if (e != hipSuccess) buf_free(h, p);
+    return e;
+}
+template <class... Bufs>
+int alloc_group(dash_t* h, const char* what, Bufs&&... bufs) {
+    const hipError_t e = alloc_all(h, bufs...);
+    return e == hipSuccess ? DASH_OK : hip_fail(h, e, what);
+}
+
+// p := n elements, unless it already holds at least that many (have); what it held is not kept
+template <class T>
+int grow(dash_t* h, T*& p, uint64_t& have, uint64_t n, const char* what) {
+    if (p && have >= n) return DASH_OK;
+    const hipError_t e = buf_alloc(h, p, n);
+    have = e == hipSuccess ? n : 0;
+    return e == hipSuccess ? DASH_OK : hip_fail(h, e, what);
+}
+
+// the per-system seed buffer (micro: the (seed, weights) pairs), allocated on first use and kept
+inline int ensure_seeds(dash_t* h, bool micro) {
+    uint64_t*& d = micro ? h->d_mseeds : h->d_seeds;
+    if (d) return DASH_OK;
+    const hipError_t e = buf_alloc(h, d, (micro ? 2 : 1) * h->cfg.num_systems);
+    return e == hipSuccess ? DASH_OK : hip_fail(h, e, micro ? "hipMalloc(micro seeds)" : "hipMalloc(seeds)");
+}
+
+// the first n events of t exist: created on first use and entered into the handle's list
+inline hipError_t timer_ready(dash_t* h, stage_timer& t, int n) {
+    for (int i = 0; i < n; i++) {
+        if (t.ev[i]) continue;
+        hipEvent_t* slot = std::find(std::begin(h->events), std::end(h->events), nullptr);
+        if (slot == std::end(h->events)) return hipErrorOutOfMemory;
+        const hipError_t e = hipEventCreate(&t.ev[i]);
+        if (e != hipSuccess) return e;
+        *slot = t.ev[i];
+    }
+    return hipSuccess;
+}
+
+// the overflow hint no longer applies (below, and dash_run when its first tier changed)
 inline hipError_t reset_hint(dash_t* h) {
     if (h->hint_n == 0) return hipSuccess;
     h->hint_n = 0;
     h->hint_tier = -1;
     return hipMemsetAsync(h->d_skip, 0, std::max<uint64_t>(h->cfg.num_systems, 1), h->stream);
+}
+
+// The traces changed, or are about to be written in place: earlier results no longer stand, and
+// neither does the overflow hint, whose memset is enqueued here. rehint = false: a load that has
+// only begun; it calls again once the new traces are on the stream.
+inline hipError_t traces_changed(dash_t* h, bool rehint = true) {
+    h->ran = false;
+    return rehint ? reset_hint(h) : hipSuccess;
+}
+
+// What the runs follow changed: earlier results no longer stand. rehint: which systems overflow a
+// tier depends on their schedules, so the overflow hint of earlier runs is void too.
+inline hipError_t schedule_changed(dash_t* h, sched_src src, bool rehint) {
+    h->follow = src;
+    h->ran = false;
+    return rehint ? reset_hint(h) : hipSuccess;
+}
+
+// One pass of a search that wrote its traces or seeds on the device: the handle follows *follow from
+// here on (nullptr: only the traces changed), then dash_run, which returns with the stream idle;
+// its kernel time is added to sim_ms.
+inline int run_pass(dash_t* h, const sched_src* follow, double& sim_ms) {
+    HIPCHK(h, follow ? schedule_changed(h, *follow, true) : traces_changed(h));
+    dash_stats st;
+    if (int rc = dash_run(h, &st)) return rc;
+    sim_ms += st.kernel_ms;
+    return DASH_OK;
+}
+
+// One pass of the host-driven search over seeds, as for_each_seed_pass hands it on: the seeds of all
+// systems, of which the first `fresh` are new (the others repeat them), and those systems' results.
+struct seed_pass {
+    uint64_t base, fresh;  // the pass covers items [base, base + fresh) of the search
+    const uint64_t* seeds;
+    const uint64_t* digests;
+    const uint32_t* rounds;
+    const uint32_t* errors;
+};
+
+// dash_explore, dash_explore_micro and dash_check_outcomes: every system becomes a copy of src; then,
+// num_systems items per pass, system i follows seed_of(item) (weights == nullptr: a seeded round
+// schedule, dash_set_system_seeds; else a seeded micro-step schedule under that one vector,
+// dash_set_micro_seeds), the batch runs and body(seed_pass) takes the results of the new items. The
+// last pass pads with repeats of its own items.
+template <class SeedOf, class Body>
+int for_each_seed_pass(dash_t* h, uint64_t src, uint64_t n, const uint64_t* weights, SeedOf&& seed_of, Body&& body) {
+    const uint64_t nsys = h->cfg.num_systems;
+    int rc = dash_broadcast_system(h, src);
+    if (rc != DASH_OK) return rc;
+    std::vector<uint64_t> seeds(nsys), dig(nsys), wts(weights ? nsys : 0, weights ? *weights : 0);
+    std::vector<uint32_t> rnd(nsys), err(nsys);
+    for (uint64_t base = 0; base < n; base += nsys) {
+        const uint64_t fresh = std::min<uint64_t>(nsys, n - base);
+        for (uint64_t i = 0; i < nsys; i++) seeds[i] = seed_of(base + i % fresh);
+        rc = weights ? dash_set_micro_seeds(h, seeds.data(), wts.data(), nsys)
+                     : dash_set_system_seeds(h, seeds.data(), nsys);
+        if (rc != DASH_OK) return rc;
+        if ((rc = dash_run(h, nullptr)) != DASH_OK) return rc;
+        if ((rc = dash_read_results(h, 0, fresh, dig.data(), rnd.data(), err.data())) != DASH_OK) return rc;
+        if ((rc = body(seed_pass{base, fresh, seeds.data(), dig.data(), rnd.data(), err.data()})) != DASH_OK) return rc;
+    }
+    return DASH_OK;
+}
+
+// the least power of two >= n
+inline uint64_t next_pow2(uint64_t n) {
+    uint64_t p = 1;
+    while (p < n) p <<= 1;
+    return p;
+}
+
+// a micro-step weight vector: every node's weight is at most 31
+inline bool weights_valid(uint64_t w) { return !(w & 0xE0E0E0E0E0E0E0E0ull); }
+
+// words at or past a row's length have no defined content on the device: they read as 0
+inline void zero_past_lens(uint16_t* packed, uint64_t stride, uint64_t rows, const uint32_t* lens) {
+    for (uint64_t r = 0; r < rows; r++)
+        if (stride > lens[r]) memset(packed + r * stride + lens[r], 0, (size_t)(stride - lens[r]) * 2);
+}
+
+// `rows` consecutive lane rows from src_row on, out to packed at `stride` words per row, zeroed past
+// each row's length. The stream is idle afterwards.
+inline int copy_rows_out(dash_t* h, const uint2* src_row, uint64_t rows, const uint32_t* lens, uint16_t* packed,
+                         uint64_t stride) {
+    const uint64_t pitch = (uint64_t)h->nchunks * 8;  // device row stride in bytes
+    const uint64_t width = std::min<uint64_t>(stride * 2, pitch);
+    if (rows && width) {
+        HIPCHK(h, hipMemcpy2DAsync(packed, stride * 2, src_row, pitch, width, rows, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    zero_past_lens(packed, stride, rows, lens);
+    return DASH_OK;
 }
 
 // dash_check_coherence up to and including its launch, without the copy of the totals and the wait

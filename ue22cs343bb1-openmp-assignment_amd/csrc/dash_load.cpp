@@ -73,49 +73,44 @@ int dash_load_dirs(dash_t* h, const char* const* dirs, uint64_t n) {
 // loaded is gone from here on. Then the device buffers for a launch over `files` files and
 // `bytes` of text, the events, and the first-failure cell, cleared.
 static int ingest_begin(dash_t* h, uint64_t bytes, uint64_t files) {
-    h->ingest = dash_ingest_report{};
+    h->ingest.report = dash_ingest_report{};
     h->loaded = false;
-    h->ran = false;
+    HIPCHK(h, traces_changed(h, false));  // the hint goes once the new traces are on the stream
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (!h->d_fail) HIPCHK(h, buf_alloc(h, h->d_fail, 1));
-    for (auto& slab : h->iev)
-        for (hipEvent_t& e : slab)
-            if (!e) HIPCHK(h, hipEventCreate(&e));
-    if (bytes > h->d_text_cap || !h->d_text) {
+    if (!h->ingest.d_fail) HIPCHK(h, buf_alloc(h, h->ingest.d_fail, 1));
+    for (stage_timer& t : h->ingest.timer) HIPCHK(h, timer_ready(h, t, 3));
+    if (bytes > h->ingest.text_cap || !h->ingest.d_text) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        h->d_text_cap = 0;
+        h->ingest.text_cap = 0;
         const uint64_t cap = std::max<uint64_t>(bytes, 16);
-        if (buf_alloc(h, h->d_text, cap) != hipSuccess)
+        if (buf_alloc(h, h->ingest.d_text, cap) != hipSuccess)
             return fail(h, DASH_ENOMEM, "text slab of %llu bytes: out of device memory", (unsigned long long)bytes);
-        h->d_text_cap = cap;
+        h->ingest.text_cap = cap;
     }
-    if (files > h->d_files_cap || !h->d_foff) {
+    if (files > h->ingest.files_cap || !h->ingest.d_foff) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        h->d_files_cap = 0;
+        h->ingest.files_cap = 0;
         const uint64_t cap = std::max<uint64_t>(files, 1);
-        if (buf_alloc(h, h->d_foff, cap) != hipSuccess || buf_alloc(h, h->d_flen, cap) != hipSuccess)
+        if (buf_alloc(h, h->ingest.d_foff, cap) != hipSuccess || buf_alloc(h, h->ingest.d_flen, cap) != hipSuccess)
             return fail(h, DASH_ENOMEM, "file table of %llu entries: out of device memory", (unsigned long long)cap);
-        h->d_files_cap = cap;
+        h->ingest.files_cap = cap;
     }
-    HIPCHK(h, hipMemsetAsync(h->d_fail, 0xFF, sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->ingest.d_fail, 0xFF, sizeof(unsigned long long), h->stream));
     return DASH_OK;
 }
 
 // slab e's events have completed: its copy and its parse, added to the report
 static int ingest_times(dash_t* h, int e) {
-    float c = 0.f, p = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&c, h->iev[e][0], h->iev[e][1]));
-    HIPCHK(h, hipEventElapsedTime(&p, h->iev[e][1], h->iev[e][2]));
-    h->ingest.copy_ms += c;
-    h->ingest.parse_ms += p;
+    HIPCHK(h, h->ingest.timer[e].add(0, 1, h->ingest.report.copy_ms));
+    HIPCHK(h, h->ingest.timer[e].add(1, 2, h->ingest.report.parse_ms));
     return DASH_OK;
 }
 
 static dash::IngestArgs ingest_args(dash_t* h, uint64_t file_base, uint64_t files) {
     dash::IngestArgs a{};
-    a.text = h->d_text;
-    a.offsets = h->d_foff;
-    a.lengths = h->d_flen;
+    a.text = h->ingest.d_text;
+    a.offsets = h->ingest.d_foff;
+    a.lengths = h->ingest.d_flen;
     a.file_base = file_base;
     a.num_files = files;
     a.trace = reinterpret_cast<uint16_t*>(h->d_trace);
@@ -124,7 +119,7 @@ static dash::IngestArgs ingest_args(dash_t* h, uint64_t file_base, uint64_t file
     a.seg = h->seg;
     a.num_procs = h->cfg.num_procs;
     a.max_instr = h->cfg.max_instr;
-    a.fail = h->d_fail;
+    a.fail = h->ingest.d_fail;
     return a;
 }
 
@@ -134,7 +129,7 @@ static dash::IngestArgs ingest_args(dash_t* h, uint64_t file_base, uint64_t file
 static int ingest_finish(dash_t* h, const char* what, unsigned long long cell, uint64_t eio_file,
                          const char* const* dirs) {
     const uint32_t N = h->cfg.num_procs;
-    dash_ingest_report& r = h->ingest;
+    dash_ingest_report& r = h->ingest.report;
     r.rc = DASH_OK;
     r.record = 0;
     r.file = 0;
@@ -177,20 +172,21 @@ int dash_load_text(dash_t* h, const char* text, const uint64_t* offsets, const u
         int rc = ingest_begin(h, bytes, num_files);
         if (rc != DASH_OK) return rc;
         unsigned long long cell = dash::INGEST_NO_FAILURE;
-        HIPCHK(h, hipEventRecord(h->iev[0][0], h->stream));
-        if (bytes) HIPCHK(h, hipMemcpyAsync(h->d_text, text, bytes, hipMemcpyHostToDevice, h->stream));
+        const stage_timer& timer = h->ingest.timer[0];
+        HIPCHK(h, timer.mark(0, h->stream));
+        if (bytes) HIPCHK(h, hipMemcpyAsync(h->ingest.d_text, text, bytes, hipMemcpyHostToDevice, h->stream));
         if (num_files) {
-            HIPCHK(h, hipMemcpyAsync(h->d_foff, offsets, num_files * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(h->d_flen, lengths, num_files * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(h->ingest.d_foff, offsets, num_files * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(h->ingest.d_flen, lengths, num_files * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
         }
-        HIPCHK(h, hipEventRecord(h->iev[0][1], h->stream));
+        HIPCHK(h, timer.mark(1, h->stream));
         HIPCHK(h, dash::launch_ingest(ingest_args(h, 0, num_files), h->stream));
-        HIPCHK(h, hipEventRecord(h->iev[0][2], h->stream));
-        HIPCHK(h, reset_hint(h));
-        HIPCHK(h, hipMemcpyAsync(&cell, h->d_fail, sizeof cell, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, timer.mark(2, h->stream));
+        HIPCHK(h, traces_changed(h));
+        HIPCHK(h, hipMemcpyAsync(&cell, h->ingest.d_fail, sizeof cell, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         if ((rc = ingest_times(h, 0)) != DASH_OK) return rc;
-        h->ingest.text_bytes = bytes;
+        h->ingest.report.text_bytes = bytes;
         return ingest_finish(h, "dash_load_text", cell, ~0ull, nullptr);
     });
 }
@@ -209,21 +205,21 @@ int dash_load_dirs_device(dash_t* h, const char* const* dirs, uint64_t n) {
         const uint64_t slab_files = per_slab * N, slab_cap = slab_files * slot;
         int rc = ingest_begin(h, slab_cap, slab_files);
         if (rc != DASH_OK) return rc;
-        if (h->pin_cap < slab_cap || h->pin_files_cap < slab_files) {
-            h->pin_cap = h->pin_files_cap = 0;
+        if (h->ingest.pin_cap < slab_cap || h->ingest.pin_files_cap < slab_files) {
+            h->ingest.pin_cap = h->ingest.pin_files_cap = 0;
             for (int i = 0; i < 2; i++) {  // both old slabs go before a new one comes
-                buf_free(h, h->pin[i]);
-                buf_free(h, h->pin_off[i]);
-                buf_free(h, h->pin_len[i]);
+                buf_free(h, h->ingest.pin[i]);
+                buf_free(h, h->ingest.pin_off[i]);
+                buf_free(h, h->ingest.pin_len[i]);
             }
             for (int i = 0; i < 2; i++)
-                if (buf_alloc(h, h->pin[i], slab_cap, true) != hipSuccess ||
-                    buf_alloc(h, h->pin_off[i], slab_files, true) != hipSuccess ||
-                    buf_alloc(h, h->pin_len[i], slab_files, true) != hipSuccess)
+                if (buf_alloc(h, h->ingest.pin[i], slab_cap, true) != hipSuccess ||
+                    buf_alloc(h, h->ingest.pin_off[i], slab_files, true) != hipSuccess ||
+                    buf_alloc(h, h->ingest.pin_len[i], slab_files, true) != hipSuccess)
                     return fail(h, DASH_ENOMEM, "dash_load_dirs_device: two pinned slabs of %llu bytes: out of memory",
                                 (unsigned long long)slab_cap);
-            h->pin_cap = slab_cap;
-            h->pin_files_cap = slab_files;
+            h->ingest.pin_cap = slab_cap;
+            h->ingest.pin_files_cap = slab_files;
         }
         const unsigned max_threads = host_threads(std::max<uint64_t>(n, 1));
         std::atomic<uint64_t> eio{~0ull};  // lowest file the readers could not open
@@ -231,7 +227,7 @@ int dash_load_dirs_device(dash_t* h, const char* const* dirs, uint64_t n) {
         bool pending[2] = {false, false};
         auto drain = [&](int e) -> int {  // slab e's copy and parse are done: its pinned slab is free
             if (!pending[e]) return DASH_OK;
-            HIPCHK(h, hipEventSynchronize(h->iev[e][2]));
+            HIPCHK(h, hipEventSynchronize(h->ingest.timer[e].ev[2]));
             pending[e] = false;
             return ingest_times(h, e);
         };
@@ -240,9 +236,9 @@ int dash_load_dirs_device(dash_t* h, const char* const* dirs, uint64_t n) {
             if ((rc = drain(e)) != DASH_OK) return rc;
             const uint64_t cnt = std::min(per_slab, n - s0);
             const unsigned nt = (unsigned)std::min<uint64_t>(max_threads, cnt);
-            char* slab = h->pin[e];
-            uint64_t* off = h->pin_off[e];
-            uint32_t* len = h->pin_len[e];
+            char* slab = h->ingest.pin[e];
+            uint64_t* off = h->ingest.pin_off[e];
+            uint32_t* len = h->ingest.pin_len[e];
             std::vector<uint64_t> used(nt, 0);
             // reader j: systems [s0 + cnt * j / nt, s0 + cnt * (j + 1) / nt), back to back from
             // its region's start, each file on a 16-byte boundary (dash_read_dirs_text's layout)
@@ -275,23 +271,23 @@ int dash_load_dirs_device(dash_t* h, const char* const* dirs, uint64_t n) {
             };
             const auto t0 = std::chrono::steady_clock::now();
             run_indexed(nt, reader);
-            h->ingest.read_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            HIPCHK(h, hipEventRecord(h->iev[e][0], h->stream));
+            h->ingest.report.read_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            HIPCHK(h, h->ingest.timer[e].mark(0, h->stream));
             for (unsigned j = 0; j < nt; j++) {
                 const uint64_t region = (cnt * j / nt) * N * slot;
                 if (used[j])
-                    HIPCHK(h, hipMemcpyAsync(h->d_text + region, slab + region, used[j], hipMemcpyHostToDevice, h->stream));
-                h->ingest.text_bytes += used[j];
+                    HIPCHK(h, hipMemcpyAsync(h->ingest.d_text + region, slab + region, used[j], hipMemcpyHostToDevice, h->stream));
+                h->ingest.report.text_bytes += used[j];
             }
-            HIPCHK(h, hipMemcpyAsync(h->d_foff, off, cnt * N * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(h->d_flen, len, cnt * N * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipEventRecord(h->iev[e][1], h->stream));
+            HIPCHK(h, hipMemcpyAsync(h->ingest.d_foff, off, cnt * N * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(h->ingest.d_flen, len, cnt * N * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, h->ingest.timer[e].mark(1, h->stream));
             HIPCHK(h, dash::launch_ingest(ingest_args(h, s0 * N, cnt * N), h->stream));
-            HIPCHK(h, hipEventRecord(h->iev[e][2], h->stream));
+            HIPCHK(h, h->ingest.timer[e].mark(2, h->stream));
             pending[e] = true;
         }
-        HIPCHK(h, reset_hint(h));
-        HIPCHK(h, hipMemcpyAsync(&cell, h->d_fail, sizeof cell, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, traces_changed(h));
+        HIPCHK(h, hipMemcpyAsync(&cell, h->ingest.d_fail, sizeof cell, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         if ((rc = drain(0)) != DASH_OK || (rc = drain(1)) != DASH_OK) return rc;
         return ingest_finish(h, "dash_load_dirs_device", cell, eio.load(), dirs);
@@ -300,7 +296,7 @@ int dash_load_dirs_device(dash_t* h, const char* const* dirs, uint64_t n) {
 
 int dash_ingest_info(const dash_t* h, dash_ingest_report* out) {
     if (!h || !out) return DASH_EINVAL;
-    *out = h->ingest;
+    *out = h->ingest.report;
     return DASH_OK;
 }
 

@@ -17,18 +17,11 @@ int dash_compute_metrics(dash_t* h, dash_metrics_totals* totals) {
         if (!h->d_events) return fail(h, DASH_ESTATE, "created with trace_events = 0");
         const uint64_t nsys = h->cfg.num_systems;
         HIPCHK(h, hipSetDevice(h->cfg.device));
-        if (!h->d_metrics) {
-            hipError_t e = buf_alloc(h, h->d_metrics, nsys * h->cfg.num_procs * 4);
-            if (e == hipSuccess) e = buf_alloc(h, h->d_metrics_cut, nsys);
-            if (e == hipSuccess) e = buf_alloc(h, h->d_metrics_tot, dash::TOT_WORDS);
-            if (e != hipSuccess) {
-                buf_free(h, h->d_metrics);
-                buf_free(h, h->d_metrics_cut);
-                buf_free(h, h->d_metrics_tot);
-                return hip_fail(h, e, "hipMalloc(metrics)");
-            }
-        }
-        h->metrics = false;
+        if (!h->met.d_rec)
+            if (int rc = alloc_group(h, "hipMalloc(metrics)", h->met.d_rec, nsys * h->cfg.num_procs * 4, h->met.d_cut, nsys,
+                                     h->met.d_tot, dash::TOT_WORDS))
+                return rc;
+        h->met.valid = false;
         dash::MetricsArgs a{};
         a.events = h->d_events;
         a.rounds = h->d_rounds;
@@ -36,15 +29,15 @@ int dash_compute_metrics(dash_t* h, dash_metrics_totals* totals) {
         a.num_procs = h->cfg.num_procs;
         a.seg = h->seg;
         a.ev_rounds = h->ev_rounds;
-        a.records = h->d_metrics;
-        a.truncated = h->d_metrics_cut;
-        a.totals = h->d_metrics_tot;
+        a.records = h->met.d_rec;
+        a.truncated = h->met.d_cut;
+        a.totals = h->met.d_tot;
         unsigned long long t[dash::TOT_WORDS];
-        HIPCHK(h, hipMemsetAsync(h->d_metrics_tot, 0, sizeof t, h->stream));
+        HIPCHK(h, hipMemsetAsync(h->met.d_tot, 0, sizeof t, h->stream));
         HIPCHK(h, dash::launch_metrics(a, h->groups, h->stream));
-        HIPCHK(h, hipMemcpyAsync(t, h->d_metrics_tot, sizeof t, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(t, h->met.d_tot, sizeof t, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        h->metrics = true;
+        h->met.valid = true;
         if (totals) memcpy(totals, t, sizeof *totals);
         return DASH_OK;
     });
@@ -52,15 +45,15 @@ int dash_compute_metrics(dash_t* h, dash_metrics_totals* totals) {
 
 int dash_read_metrics(dash_t* h, uint64_t first, uint64_t count, dash_node_metrics* out, uint8_t* truncated) {
     if (!h || (!out && count)) return DASH_EINVAL;
-    if (!h->ran || !h->metrics) return fail(h, DASH_ESTATE, "no dash_compute_metrics since the last dash_run");
+    if (!h->ran || !h->met.valid) return fail(h, DASH_ESTATE, "no dash_compute_metrics since the last dash_run");
     if (first + count > h->cfg.num_systems || first + count < first) return fail(h, DASH_EINVAL, "range out of bounds");
     const uint32_t N = h->cfg.num_procs;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (count) {
-        HIPCHK(h, hipMemcpyAsync(out, h->d_metrics + first * N * 4, count * N * sizeof *out, hipMemcpyDeviceToHost,
+        HIPCHK(h, hipMemcpyAsync(out, h->met.d_rec + first * N * 4, count * N * sizeof *out, hipMemcpyDeviceToHost,
                                  h->stream));
         if (truncated)
-            HIPCHK(h, hipMemcpyAsync(truncated, h->d_metrics_cut + first, count, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipMemcpyAsync(truncated, h->met.d_cut + first, count, hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return DASH_OK;

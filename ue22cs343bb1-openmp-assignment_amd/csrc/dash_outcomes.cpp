@@ -13,23 +13,6 @@ static_assert(offsetof(dash_outcome_ex, coh) == offsetof(dash::OutcomeOut, coh) 
                   offsetof(dash_outcome, rounds) == offsetof(dash::OutcomeOut, rounds),
               "field for field");
 
-static uint64_t next_pow2_64(uint64_t n) {
-    uint64_t p = 1;
-    while (p < n) p <<= 1;
-    return p;
-}
-
-// p := n elements, unless it already holds at least that many (have)
-template <class T>
-static int grow(dash_t* h, T*& p, uint64_t& have, uint64_t n, size_t elem, const char* what) {
-    if (p && have >= n) return DASH_OK;
-    uint8_t* raw = reinterpret_cast<uint8_t*>(p);
-    const hipError_t e = buf_alloc(h, raw, std::max<uint64_t>(n, 1) * elem);
-    p = reinterpret_cast<T*>(raw);
-    have = e == hipSuccess ? n : 0;
-    return e == hipSuccess ? DASH_OK : hip_fail(h, e, what);
-}
-
 extern "C" int dash_explore_sources(dash_t* h, uint64_t num_sources, uint64_t first_seed, uint64_t seeds_per_source,
                                     const uint64_t* weights, uint64_t table_slots, dash_outcome_ex* out, uint64_t cap,
                                     uint64_t* n, dash_source_summary* per_source, dash_explore_totals* totals) {
@@ -46,103 +29,76 @@ extern "C" int dash_explore_sources(dash_t* h, uint64_t num_sources, uint64_t fi
         if (G == 0 || G > S)
             return fail(h, DASH_EINVAL, "%s: %llu sources for %llu systems", what, (unsigned long long)G,
                         (unsigned long long)S);
-        if (weights && (*weights & 0xE0E0E0E0E0E0E0E0ull)) return fail(h, DASH_EINVAL, "%s: a weight above 31", what);
+        if (weights && !weights_valid(*weights)) return fail(h, DASH_EINVAL, "%s: a weight above 31", what);
         if (K > UINT64_MAX - F) return fail(h, DASH_EINVAL, "%s: first_seed + seeds_per_source wraps", what);
         const uint64_t R = S / G, passes = K / R + (K % R != 0);
         const uint64_t schedules = K > UINT64_MAX / G ? UINT64_MAX : G * K;  // saturated: only sizes use it
-        const uint64_t slots = table_slots ? next_pow2_64(std::min(table_slots, dash::MAX_SLOTS))
-                                           : std::max<uint64_t>(64, next_pow2_64(2 * std::min<uint64_t>(schedules, 1ull << 21)));
+        const uint64_t slots = table_slots ? next_pow2(std::min(table_slots, dash::MAX_SLOTS))
+                                           : std::max<uint64_t>(64, next_pow2(2 * std::min<uint64_t>(schedules, 1ull << 21)));
         if (table_slots > dash::MAX_SLOTS) return fail(h, DASH_EINVAL, "%s: table_slots above 2^31", what);
         const uint64_t out_cap = std::max<uint64_t>(std::min(slots, schedules), 1);  // outcomes <= schedules
 
         HIPCHK(h, hipSetDevice(h->cfg.device));
-        dash::OutcomeSlot* table = static_cast<dash::OutcomeSlot*>(h->d_oc_table);
-        dash::OutcomeOut* dense = static_cast<dash::OutcomeOut*>(h->d_oc_out);
-        int rc = grow(h, table, h->oc_slots, slots, sizeof *table, "hipMalloc(outcome table)");
-        h->d_oc_table = table;
+        int rc = grow(h, h->oc.d_table, h->oc.slots, slots, "hipMalloc(outcome table)");
+        if (rc == DASH_OK) rc = grow(h, h->oc.d_out, h->oc.out_cap, out_cap, "hipMalloc(outcomes)");
+        if (rc == DASH_OK && !h->oc.d_place)
+            rc = alloc_group(h, "hipMalloc(outcome scratch)", h->oc.d_place, S, h->oc.d_counters, dash::OC_WORDS);
+        if (rc == DASH_OK) rc = ensure_seeds(h, weights != nullptr);
         if (rc != DASH_OK) return rc;
-        rc = grow(h, dense, h->oc_out_cap, out_cap, sizeof *dense, "hipMalloc(outcomes)");
-        h->d_oc_out = dense;
-        if (rc != DASH_OK) return rc;
-        if (!h->d_oc_place) {
-            hipError_t e = buf_alloc(h, h->d_oc_place, S);
-            if (e == hipSuccess) e = buf_alloc(h, h->d_oc_counters, dash::OC_WORDS);
-            if (e != hipSuccess) {
-                buf_free(h, h->d_oc_place);
-                buf_free(h, h->d_oc_counters);
-                return hip_fail(h, e, "hipMalloc(outcome scratch)");
-            }
-        }
-        uint64_t*& d_seeds = weights ? h->d_mseeds : h->d_seeds;
-        if (!d_seeds) {
-            const hipError_t e = buf_alloc(h, d_seeds, weights ? 2 * S : S);
-            if (e != hipSuccess) return hip_fail(h, e, "hipMalloc(seeds)");
-        }
-        for (hipEvent_t& e : h->oc_ev)
-            if (!e) HIPCHK(h, hipEventCreate(&e));
-        hipEvent_t* ev = h->oc_ev;
-        auto elapsed = [&](hipEvent_t a, hipEvent_t b, double& sum) -> hipError_t {
-            float ms = 0.f;
-            const hipError_t e = hipEventElapsedTime(&ms, a, b);
-            sum += ms;
-            return e;
-        };
+        stage_timer& timer = h->oc.timer;
+        HIPCHK(h, timer_ready(h, timer, 5));
+        dash::OutcomeSlot* const table = h->oc.d_table;
+        dash::OutcomeOut* const dense = h->oc.d_out;
+        uint64_t* const d_seeds = weights ? h->d_mseeds : h->d_seeds;
 
         double sim_ms = 0, merge_ms = 0, insert_ms = 0;
         const sched_src src = weights ? sched_src::micro_seeds : sched_src::system_seeds;
-        // before the first pass: the copies of the sources and an empty table. The traces changed and
-        // the seeds will: earlier results and the overflow hint no longer stand.
-        HIPCHK(h, hipEventRecord(ev[0], h->stream));
+        // before the first pass: the copies of the sources and an empty table
+        HIPCHK(h, timer.mark(0, h->stream));
         HIPCHK(h, dash::launch_replicate(h->d_trace, h->d_lens, S, G, (uint64_t)h->seg * h->nchunks, h->cfg.num_procs,
                                          h->stream));
-        HIPCHK(h, dash::launch_clear_table(table, slots, h->d_oc_counters, h->stream));
-        HIPCHK(h, reset_hint(h));
-        h->ran = false;
+        HIPCHK(h, dash::launch_clear_table(table, slots, h->oc.d_counters, h->stream));
+        HIPCHK(h, traces_changed(h));
         for (uint64_t p = 0; p < passes; p++) {
             const dash::AssignArgs a{S, G, K, F, R, p * R};
-            if (p) HIPCHK(h, hipEventRecord(ev[0], h->stream));
+            if (p) HIPCHK(h, timer.mark(0, h->stream));
             HIPCHK(h, dash::launch_fill_seeds(d_seeds, a, weights ? 1u : 0u, weights ? *weights : 0, h->stream));
-            HIPCHK(h, hipEventRecord(ev[1], h->stream));
+            HIPCHK(h, timer.mark(1, h->stream));
             // the handle now follows per-system seeds, as dash_set_system_seeds / dash_set_micro_seeds
             // leave it (the kernels above run before dash_run's on the same stream)
-            HIPCHK(h, reset_hint(h));
-            h->follow = src;
-            h->ran = false;
-            dash_stats st;
-            if ((rc = dash_run(h, &st)) != DASH_OK) return rc;  // returns with the stream idle
-            sim_ms += st.kernel_ms;
-            HIPCHK(h, elapsed(ev[0], ev[1], merge_ms));
+            if ((rc = run_pass(h, &src, sim_ms)) != DASH_OK) return rc;
+            HIPCHK(h, timer.add(0, 1, merge_ms));
             if (p) {  // the previous pass's merge
-                HIPCHK(h, elapsed(ev[2], ev[3], merge_ms));
-                HIPCHK(h, elapsed(ev[2], ev[4], insert_ms));
+                HIPCHK(h, timer.add(2, 3, merge_ms));
+                HIPCHK(h, timer.add(2, 4, insert_ms));
             }
-            HIPCHK(h, hipEventRecord(ev[2], h->stream));
+            HIPCHK(h, timer.mark(2, h->stream));
             const uint32_t group_keys = (h->cfg.flags & DASH_TEST_INSERT_PER_LANE)  ? 0u
                                         : (h->cfg.flags & DASH_TEST_INSERT_GROUPS) ? 64u
                                                                                    : dash::GROUP_KEYS;
-            HIPCHK(h, dash::launch_insert(a, h->d_digests, h->d_errors, table, slots, h->d_oc_place, h->d_oc_counters,
+            HIPCHK(h, dash::launch_insert(a, h->d_digests, h->d_errors, table, slots, h->oc.d_place, h->oc.d_counters,
                                           group_keys, h->stream));
-            HIPCHK(h, hipEventRecord(ev[4], h->stream));
+            HIPCHK(h, timer.mark(4, h->stream));
             if ((rc = coherence_enqueue(h)) != DASH_OK) return rc;
-            HIPCHK(h, dash::launch_witness(a, h->d_oc_place, h->d_rounds, h->d_coh, table, h->stream));
-            HIPCHK(h, hipEventRecord(ev[3], h->stream));
+            HIPCHK(h, dash::launch_witness(a, h->oc.d_place, h->d_rounds, h->coh.d_rec, table, h->stream));
+            HIPCHK(h, timer.mark(3, h->stream));
         }
-        if (passes == 0) HIPCHK(h, hipEventRecord(ev[1], h->stream));
+        if (passes == 0) HIPCHK(h, timer.mark(1, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         if (passes) {
-            h->coherence = true;  // the records of the last pass
-            HIPCHK(h, elapsed(ev[2], ev[3], merge_ms));
-            HIPCHK(h, elapsed(ev[2], ev[4], insert_ms));
+            h->coh.valid = true;  // the records of the last pass
+            HIPCHK(h, timer.add(2, 3, merge_ms));
+            HIPCHK(h, timer.add(2, 4, insert_ms));
         } else {
-            HIPCHK(h, elapsed(ev[0], ev[1], merge_ms));
+            HIPCHK(h, timer.add(0, 1, merge_ms));
         }
         unsigned long long counters[dash::OC_WORDS];
-        HIPCHK(h, hipEventRecord(ev[0], h->stream));
-        HIPCHK(h, dash::launch_compact(table, slots, dense, out_cap, h->d_oc_counters, h->stream));
-        HIPCHK(h, hipEventRecord(ev[1], h->stream));
-        HIPCHK(h, hipMemcpyAsync(counters, h->d_oc_counters, sizeof counters, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, timer.mark(0, h->stream));
+        HIPCHK(h, dash::launch_compact(table, slots, dense, out_cap, h->oc.d_counters, h->stream));
+        HIPCHK(h, timer.mark(1, h->stream));
+        HIPCHK(h, hipMemcpyAsync(counters, h->oc.d_counters, sizeof counters, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, elapsed(ev[0], ev[1], merge_ms));
+        HIPCHK(h, timer.add(0, 1, merge_ms));
         const uint64_t found = counters[dash::OC_OUTCOMES];
         if (found > out_cap) return fail(h, DASH_EDEVICE, "%s: %llu outcomes of at most %llu", what,
                                          (unsigned long long)found, (unsigned long long)out_cap);

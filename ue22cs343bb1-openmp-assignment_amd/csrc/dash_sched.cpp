@@ -23,14 +23,11 @@ static int table_fits(dash_t* h, const char* what, uint32_t rounds) {
     return DASH_OK;
 }
 
-// The end of every call that changes what the runs follow: the stream's work (uploads, the
-// table kernel) is done and earlier results no longer stand. rehint: which systems overflow a
-// tier depends on their schedules, so the overflow hint of earlier runs is void too.
+// The end of every call that changes what the runs follow: schedule_changed, and the stream's
+// work (uploads, the table kernel, the hint's memset) is done.
 static int follow_now(dash_t* h, sched_src src, bool rehint) {
-    if (rehint) HIPCHK(h, reset_hint(h));
+    HIPCHK(h, schedule_changed(h, src, rehint));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->follow = src;
-    h->ran = false;
     return DASH_OK;
 }
 
@@ -54,13 +51,10 @@ static int unset_seeds(dash_t* h, const char* what, uint64_t n, bool rehint) {
     return follow_now(h, sched_src::round_table, rehint);
 }
 
-// v[words] into the seed buffer d, allocated on first use and kept
-static int upload_seeds(dash_t* h, uint64_t*& d, const char* alloc_what, const uint64_t* v, uint64_t words,
-                        sched_src src) {
-    if (!d) {
-        const hipError_t e = buf_alloc(h, d, words);
-        if (e != hipSuccess) return hip_fail(h, e, alloc_what);
-    }
+// v[words] into the seed buffer of `src` (ensure_seeds), which the runs follow from here on
+static int upload_seeds(dash_t* h, const uint64_t* v, uint64_t words, sched_src src) {
+    if (int rc = ensure_seeds(h, src == sched_src::micro_seeds)) return rc;
+    uint64_t* d = src == sched_src::micro_seeds ? h->d_mseeds : h->d_seeds;
     if (words) HIPCHK(h, hipMemcpyAsync(d, v, words * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
     return follow_now(h, src, true);
 }
@@ -139,7 +133,7 @@ int dash_set_system_seeds(dash_t* h, const uint64_t* seeds, uint64_t n) {
         if (n != h->cfg.num_systems)
             return fail(h, DASH_EINVAL, "dash_set_system_seeds: %llu seeds for %llu systems", (unsigned long long)n,
                         (unsigned long long)h->cfg.num_systems);
-        return upload_seeds(h, h->d_seeds, "hipMalloc(seeds)", seeds, n, sched_src::system_seeds);
+        return upload_seeds(h, seeds, n, sched_src::system_seeds);
     });
 }
 
@@ -155,13 +149,13 @@ int dash_set_micro_seeds(dash_t* h, const uint64_t* seeds, const uint64_t* weigh
         std::vector<uint64_t> pairs(2 * n);
         for (uint64_t k = 0; k < n; k++) {
             const uint64_t w = weights ? weights[k] : DASH_MICRO_UNIFORM;
-            if (w & 0xE0E0E0E0E0E0E0E0ull)
+            if (!weights_valid(w))
                 return fail(h, DASH_EINVAL, "dash_set_micro_seeds: system %llu: a weight above 31", (unsigned long long)k);
             pairs[2 * k] = seeds[k];
             pairs[2 * k + 1] = w;
         }
         // (micro-step runs take no tiers: the hint of earlier runs is void)
-        return upload_seeds(h, h->d_mseeds, "hipMalloc(micro seeds)", pairs.data(), pairs.size(), sched_src::micro_seeds);
+        return upload_seeds(h, pairs.data(), pairs.size(), sched_src::micro_seeds);
     });
 }
 
@@ -172,9 +166,8 @@ int dash_broadcast_system(dash_t* h, uint64_t src) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, dash::launch_broadcast(h->d_trace, h->d_lens, h->cfg.num_systems, src, (uint64_t)h->seg * h->nchunks,
                                      h->cfg.num_procs, h->stream));
-    HIPCHK(h, reset_hint(h));
+    HIPCHK(h, traces_changed(h));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->ran = false;
     return DASH_OK;
 }
 
@@ -191,32 +184,24 @@ static int explore_impl(dash_t* h, const char* what, uint64_t src, uint64_t firs
         if (!weights && h->follow == sched_src::micro_table)
             return fail(h, DASH_ESTATE, "%s: the handle follows a micro-step schedule", what);
         if (num_seeds && !nsys) return fail(h, DASH_EINVAL, "%s: the handle has no systems", what);
-        int rc = dash_broadcast_system(h, src);
-        if (rc != DASH_OK) return rc;
-        std::vector<uint64_t> seeds(nsys), dig(nsys), wts(weights ? nsys : 0, weights ? *weights : 0);
-        std::vector<uint32_t> rnd(nsys), err(nsys);
         std::vector<dash_outcome> found;
         std::map<std::pair<uint64_t, uint32_t>, size_t> index;  // (digest, errors) -> found[]
-        for (uint64_t base = 0; base < num_seeds; base += nsys) {
-            const uint64_t fresh = std::min<uint64_t>(nsys, num_seeds - base);
-            // the last pass pads with repeats of its own seeds, which are not counted
-            for (uint64_t i = 0; i < nsys; i++) seeds[i] = first_seed + base + i % fresh;
-            rc = weights ? dash_set_micro_seeds(h, seeds.data(), wts.data(), nsys)
-                         : dash_set_system_seeds(h, seeds.data(), nsys);
-            if (rc != DASH_OK) return rc;
-            if ((rc = dash_run(h, nullptr)) != DASH_OK) return rc;
-            if ((rc = dash_read_results(h, 0, nsys, dig.data(), rnd.data(), err.data())) != DASH_OK) return rc;
-            for (uint64_t i = 0; i < fresh; i++) {
-                const auto it = index.emplace(std::make_pair(dig[i], err[i]), found.size());
-                if (it.second) found.push_back(dash_outcome{dig[i], 0, seeds[i], rnd[i], err[i]});
+        auto seed_of = [&](uint64_t k) { return first_seed + k; };
+        // (the repeats that pad the last pass are not counted)
+        const int rc = for_each_seed_pass(h, src, num_seeds, weights, seed_of, [&](const seed_pass& p) -> int {
+            for (uint64_t i = 0; i < p.fresh; i++) {
+                const auto it = index.emplace(std::make_pair(p.digests[i], p.errors[i]), found.size());
+                if (it.second) found.push_back(dash_outcome{p.digests[i], 0, p.seeds[i], p.rounds[i], p.errors[i]});
                 dash_outcome& o = found[it.first->second];
                 o.count++;
-                if (seeds[i] < o.seed) {  // only when first_seed + i wrapped past 2^64
-                    o.seed = seeds[i];
-                    o.rounds = rnd[i];
+                if (p.seeds[i] < o.seed) {  // only when first_seed + i wrapped past 2^64
+                    o.seed = p.seeds[i];
+                    o.rounds = p.rounds[i];
                 }
             }
-        }
+            return DASH_OK;
+        });
+        if (rc != DASH_OK) return rc;
         std::sort(found.begin(), found.end(), [](const dash_outcome& a, const dash_outcome& b) { return a.seed < b.seed; });
         *n = (uint32_t)std::min<size_t>(found.size(), 0xFFFFFFFFu);
         for (size_t k = 0; k < found.size() && k < cap; k++) out[k] = found[k];
@@ -231,7 +216,7 @@ int dash_explore(dash_t* h, uint64_t src, uint64_t first_seed, uint64_t num_seed
 
 int dash_explore_micro(dash_t* h, uint64_t src, uint64_t first_seed, uint64_t num_seeds, uint64_t weights,
                        dash_outcome* out, uint32_t cap, uint32_t* n) {
-    if (h && (weights & 0xE0E0E0E0E0E0E0E0ull)) return fail(h, DASH_EINVAL, "dash_explore_micro: a weight above 31");
+    if (h && !weights_valid(weights)) return fail(h, DASH_EINVAL, "dash_explore_micro: a weight above 31");
     return explore_impl(h, "dash_explore_micro", src, first_seed, num_seeds, &weights, out, cap, n);
 }
 

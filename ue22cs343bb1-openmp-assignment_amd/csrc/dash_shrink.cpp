@@ -29,6 +29,28 @@ uint32_t write_chunks(const dash_t* h, uint32_t max_len) {
     return std::max<uint32_t>(1u, std::min<uint64_t>(h->nchunks, ((uint64_t)max_len + 3) / 4 + 2));
 }
 
+// One launch of the variant kernel: nsys systems from dst on are written from the base, whose longest
+// trace is max_len, as `mode` says (dash_shrink.h); SHRINK_CANDIDATES numbers them from `first` and
+// counts what each deletes, SHRINK_APPLY takes the winner from the cell.
+dash::VariantArgs variant_args(const dash_t* h, const uint2* base, const uint32_t* base_lens, uint2* dst,
+                               uint32_t* dst_lens, uint64_t nsys, uint32_t max_len, uint32_t mode, uint64_t first = 0) {
+    dash::VariantArgs a{};
+    a.base = base;
+    a.base_lens = base_lens;
+    a.dst = dst;
+    a.dst_lens = dst_lens;
+    a.dst_count = dst == h->d_trace ? h->sh.d_count : nullptr;  // the batch: what each candidate deletes
+    a.nsys = nsys;
+    a.row = (uint64_t)h->seg * h->nchunks;
+    a.first = first;
+    a.nchunks = h->nchunks;
+    a.num_procs = h->cfg.num_procs;
+    a.wchunks = write_chunks(h, max_len);
+    a.mode = mode;
+    a.cell = mode == dash::SHRINK_APPLY ? h->sh.d_cell : nullptr;
+    return a;
+}
+
 }  // namespace
 
 extern "C" int dash_shrink(dash_t* h, uint64_t src, uint64_t seed, const dash_shrink_goal* goal, uint16_t* packed_out,
@@ -52,26 +74,14 @@ extern "C" int dash_shrink(dash_t* h, uint64_t src, uint64_t seed, const dash_sh
         if (src >= S) return fail(h, DASH_EINVAL, "%s: system %llu out of range", what, (unsigned long long)src);
 
         HIPCHK(h, hipSetDevice(h->cfg.device));
-        if (!h->d_sh_base) {
-            hipError_t e = buf_alloc(h, h->d_sh_base, 2 * row);
-            if (e == hipSuccess) e = buf_alloc(h, h->d_sh_lens, 2 * DASH_MAX_PROCS);
-            if (e == hipSuccess) e = buf_alloc(h, h->d_sh_count, S);
-            if (e == hipSuccess) e = buf_alloc(h, h->d_sh_cell, 1);
-            if (e != hipSuccess) {
-                buf_free(h, h->d_sh_base);
-                buf_free(h, h->d_sh_lens);
-                buf_free(h, h->d_sh_count);
-                buf_free(h, h->d_sh_cell);
-                return hip_fail(h, e, "hipMalloc(shrink)");
-            }
-        }
-        if (h->d_arb && !h->d_seeds) {
-            const hipError_t e = buf_alloc(h, h->d_seeds, S);
-            if (e != hipSuccess) return hip_fail(h, e, "hipMalloc(seeds)");
-        }
-        for (hipEvent_t& e : h->sh_ev)
-            if (!e) HIPCHK(h, hipEventCreate(&e));
-        hipEvent_t* ev = h->sh_ev;
+        if (!h->sh.d_base)
+            if (int rc = alloc_group(h, "hipMalloc(shrink)", h->sh.d_base, 2 * row, h->sh.d_lens, 2 * DASH_MAX_PROCS,
+                                     h->sh.d_count, S, h->sh.d_cell, 1))
+                return rc;
+        if (h->d_arb)
+            if (int rc = ensure_seeds(h, false)) return rc;
+        stage_timer& timer = h->sh.timer;
+        HIPCHK(h, timer_ready(h, timer, 6));
 
         // the source's lengths: the host's copy of the base's, kept in step with the device's by decoding
         // every winner with the same function
@@ -88,79 +98,65 @@ extern "C" int dash_shrink(dash_t* h, uint64_t src, uint64_t seed, const dash_sh
         // a seeded handle follows one seed for every system (0: lockstep), as dash_set_system_seeds leaves
         // it; a handle without a schedule seed runs its plain lockstep kernel
         if (h->d_arb) HIPCHK(h, dash::launch_fill_u64(h->d_seeds, S, seed, h->stream));
+        const sched_src seeds = sched_src::system_seeds;
 
         int cur = 0;  // which of the two base rows holds the base
-        auto base_row = [&](int i) { return h->d_sh_base + (uint64_t)i * row; };
-        auto base_lens = [&](int i) { return h->d_sh_lens + i * DASH_MAX_PROCS; };
-        auto max_len = [&]() { return *std::max_element(lens, lens + N); };
-        // one launch of the variant kernel from the base over the whole batch
+        auto base_row = [&](int i) { return h->sh.d_base + (uint64_t)i * row; };
+        auto base_lens = [&](int i) { return h->sh.d_lens + i * DASH_MAX_PROCS; };
+        // one launch of the variant kernel from the base: the round's winner into the other base row
+        // (SHRINK_APPLY), else `mode` over the whole batch, from candidate `first` on
         auto variants = [&](uint32_t mode, uint64_t first) -> hipError_t {
-            dash::VariantArgs a{};
-            a.base = base_row(cur);
-            a.base_lens = base_lens(cur);
-            a.dst = h->d_trace;
-            a.dst_lens = h->d_lens;
-            a.dst_count = h->d_sh_count;
-            a.nsys = S;
-            a.row = row;
-            a.first = first;
-            a.nchunks = h->nchunks;
-            a.num_procs = N;
-            a.wchunks = write_chunks(h, max_len());
-            a.mode = mode;
-            return h->nchunks ? dash::launch_variants(a, h->stream) : hipSuccess;
+            if (!h->nchunks) return hipSuccess;
+            const uint32_t max_len = *std::max_element(lens, lens + N);
+            const bool apply = mode == dash::SHRINK_APPLY;
+            return dash::launch_variants(variant_args(h, base_row(cur), base_lens(cur), apply ? base_row(cur ^ 1) : h->d_trace,
+                                                      apply ? base_lens(cur ^ 1) : h->d_lens, apply ? 1 : S, max_len, mode, first),
+                                         h->stream);
         };
-        // the traces changed: the handle as dash_explore_sources marks it after its replicate, then the run
-        auto simulate = [&]() -> int {
-            HIPCHK(h, reset_hint(h));
-            if (h->d_arb) h->follow = sched_src::system_seeds;
-            h->ran = false;
-            dash_stats st;
-            if (int rc = dash_run(h, &st)) return rc;  // returns with the stream idle
-            rep.sim_ms += st.kernel_ms;
+        // a sub-pass after its variants (marks 0, 1): the run, then the coherence records and, for
+        // `counted` candidates from `first` on, the select (marks 2, 3). The time of marks 2, 3 is
+        // added once they have completed: at the next sub-pass, or by the caller after its wait.
+        bool select_pending = false;
+        auto run_and_check = [&](uint64_t counted, uint64_t first) -> int {
+            if (int rc = run_pass(h, h->d_arb ? &seeds : nullptr, rep.sim_ms)) return rc;  // the traces changed
             rep.passes++;
+            HIPCHK(h, timer.add(0, 1, rep.gen_ms));
+            if (select_pending) HIPCHK(h, timer.add(2, 3, rep.select_ms));
+            HIPCHK(h, timer.mark(2, h->stream));
+            if (int rc = coherence_enqueue(h)) return rc;
+            if (counted)
+                HIPCHK(h, dash::launch_select(h->d_errors, h->coh.d_rec, h->sh.d_count, counted, first, goal->coh_all,
+                                              goal->err_all, goal->err_none, h->sh.d_cell, h->stream));
+            HIPCHK(h, timer.mark(3, h->stream));
+            select_pending = true;
             return DASH_OK;
         };
-        auto elapsed = [&](int a, int b, double& sum) -> hipError_t {
-            float ms = 0.f;
-            const hipError_t e = hipEventElapsedTime(&ms, ev[a], ev[b]);
-            sum += ms;
-            return e;
+        // the wait for a sub-pass's records (and whatever was enqueued after them)
+        auto checked = [&]() -> int {
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            HIPCHK(h, timer.add(2, 3, rep.select_ms));
+            select_pending = false;
+            return DASH_OK;
         };
 
         // base row 0 := the source, cleared past its lengths; then the whole batch := the base, and its
         // run says whether the source meets the goal at all
-        HIPCHK(h, hipEventRecord(ev[0], h->stream));
-        if (h->nchunks) {
-            dash::VariantArgs a{};
-            a.base = h->d_trace + src * row;
-            a.base_lens = h->d_lens + src * N;
-            a.dst = base_row(0);
-            a.dst_lens = base_lens(0);
-            a.nsys = 1;
-            a.row = row;
-            a.nchunks = h->nchunks;
-            a.num_procs = N;
-            a.wchunks = write_chunks(h, src_max);
-            a.mode = dash::SHRINK_COPY;
-            HIPCHK(h, dash::launch_variants(a, h->stream));
-        } else {
+        HIPCHK(h, timer.mark(0, h->stream));
+        if (h->nchunks)
+            HIPCHK(h, dash::launch_variants(variant_args(h, h->d_trace + src * row, h->d_lens + src * N, base_row(0),
+                                                         base_lens(0), 1, src_max, dash::SHRINK_COPY),
+                                            h->stream));
+        else
             HIPCHK(h, hipMemsetAsync(base_lens(0), 0, DASH_MAX_PROCS * sizeof(uint32_t), h->stream));
-        }
         HIPCHK(h, variants(dash::SHRINK_COPY, 0));
-        HIPCHK(h, hipEventRecord(ev[1], h->stream));
-        if (int rc = simulate()) return rc;
-        HIPCHK(h, elapsed(0, 1, rep.gen_ms));
-        HIPCHK(h, hipEventRecord(ev[2], h->stream));
-        if (int rc = coherence_enqueue(h)) return rc;
-        HIPCHK(h, hipEventRecord(ev[3], h->stream));
+        HIPCHK(h, timer.mark(1, h->stream));
+        if (int rc = run_and_check(0, 0)) return rc;
         uint32_t src_err = 0;
         dash_coherence src_coh{};
         HIPCHK(h, hipMemcpyAsync(&src_err, h->d_errors, sizeof src_err, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(&src_coh, h->d_coh, sizeof src_coh, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        h->coherence = true;  // the batch holds copies of the source, run and checked
-        HIPCHK(h, elapsed(2, 3, rep.select_ms));
+        HIPCHK(h, hipMemcpyAsync(&src_coh, h->coh.d_rec, sizeof src_coh, hipMemcpyDeviceToHost, h->stream));
+        if (int rc = checked()) return rc;
+        h->coh.valid = true;  // the batch holds copies of the source, run and checked
         if ((src_coh.bits & goal->coh_all) != goal->coh_all || (src_err & goal->err_all) != goal->err_all ||
             (src_err & goal->err_none) != 0)
             return fail(h, DASH_EINVAL,
@@ -168,52 +164,27 @@ extern "C" int dash_shrink(dash_t* h, uint64_t src, uint64_t seed, const dash_sh
                         "coh_all 0x%X err_all 0x%X err_none 0x%X",
                         what, src_coh.bits, src_err, goal->coh_all, goal->err_all, goal->err_none);
 
-        bool select_pending = false;  // ev[2], ev[3] hold a sub-pass's select, not yet added
         for (;;) {
             dash::ShrinkCand none{};
             const uint64_t C = dash::shrink_decode(lens, N, ~0ull, none);
             if (C == 0) break;  // nothing left to delete
-            HIPCHK(h, hipMemsetAsync(h->d_sh_cell, 0, sizeof(unsigned long long), h->stream));
+            HIPCHK(h, hipMemsetAsync(h->sh.d_cell, 0, sizeof(unsigned long long), h->stream));
             for (uint64_t first = 0; first < C; first += S) {
                 const uint64_t counted = std::min<uint64_t>(S, C - first);
-                HIPCHK(h, hipEventRecord(ev[0], h->stream));
+                HIPCHK(h, timer.mark(0, h->stream));
                 HIPCHK(h, variants(dash::SHRINK_CANDIDATES, first));
-                HIPCHK(h, hipEventRecord(ev[1], h->stream));
-                if (int rc = simulate()) return rc;
-                HIPCHK(h, elapsed(0, 1, rep.gen_ms));
-                if (select_pending) HIPCHK(h, elapsed(2, 3, rep.select_ms));
-                HIPCHK(h, hipEventRecord(ev[2], h->stream));
-                if (int rc = coherence_enqueue(h)) return rc;
-                HIPCHK(h, dash::launch_select(h->d_errors, h->d_coh, h->d_sh_count, counted, first, goal->coh_all,
-                                              goal->err_all, goal->err_none, h->d_sh_cell, h->stream));
-                HIPCHK(h, hipEventRecord(ev[3], h->stream));
-                select_pending = true;
+                HIPCHK(h, timer.mark(1, h->stream));
+                if (int rc = run_and_check(counted, first)) return rc;
                 rep.variants += counted;
             }
             // the winner, if any, into the other base row; the cell says which it was
-            HIPCHK(h, hipEventRecord(ev[4], h->stream));
-            if (h->nchunks) {
-                dash::VariantArgs a{};
-                a.base = base_row(cur);
-                a.base_lens = base_lens(cur);
-                a.dst = base_row(cur ^ 1);
-                a.dst_lens = base_lens(cur ^ 1);
-                a.nsys = 1;
-                a.row = row;
-                a.nchunks = h->nchunks;
-                a.num_procs = N;
-                a.wchunks = write_chunks(h, max_len());
-                a.mode = dash::SHRINK_APPLY;
-                a.cell = h->d_sh_cell;
-                HIPCHK(h, dash::launch_variants(a, h->stream));
-            }
-            HIPCHK(h, hipEventRecord(ev[5], h->stream));
+            HIPCHK(h, timer.mark(4, h->stream));
+            HIPCHK(h, variants(dash::SHRINK_APPLY, 0));
+            HIPCHK(h, timer.mark(5, h->stream));
             unsigned long long key = 0;
-            HIPCHK(h, hipMemcpyAsync(&key, h->d_sh_cell, sizeof key, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            HIPCHK(h, elapsed(2, 3, rep.select_ms));
-            HIPCHK(h, elapsed(4, 5, rep.gen_ms));
-            select_pending = false;
+            HIPCHK(h, hipMemcpyAsync(&key, h->sh.d_cell, sizeof key, hipMemcpyDeviceToHost, h->stream));
+            if (int rc = checked()) return rc;
+            HIPCHK(h, timer.add(4, 5, rep.gen_ms));
             if (key == 0) break;  // no candidate passed: the base is 1-minimal
             dash::ShrinkCand win{};
             const uint64_t c = dash::shrink_key_candidate(key);
@@ -227,27 +198,16 @@ extern "C" int dash_shrink(dash_t* h, uint64_t src, uint64_t seed, const dash_sh
         }
 
         // every system := the minimal set, run once more with its coherence records
-        HIPCHK(h, hipEventRecord(ev[0], h->stream));
+        HIPCHK(h, timer.mark(0, h->stream));
         HIPCHK(h, variants(dash::SHRINK_COPY, 0));
-        HIPCHK(h, hipEventRecord(ev[1], h->stream));
-        if (int rc = simulate()) return rc;
-        HIPCHK(h, elapsed(0, 1, rep.gen_ms));
-        HIPCHK(h, hipEventRecord(ev[2], h->stream));
-        if (int rc = coherence_enqueue(h)) return rc;
-        HIPCHK(h, hipEventRecord(ev[3], h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        h->coherence = true;
-        HIPCHK(h, elapsed(2, 3, rep.select_ms));
+        HIPCHK(h, timer.mark(1, h->stream));
+        if (int rc = run_and_check(0, 0)) return rc;
+        if (int rc = checked()) return rc;
+        h->coh.valid = true;
 
         for (uint32_t t = 0; t < N; t++) rep.instr_after += lens[t];
-        if (packed_out && stride) {
-            const uint64_t pitch = (uint64_t)h->nchunks * 8, width = std::min<uint64_t>(stride * 2, pitch);
-            if (width) HIPCHK(h, hipMemcpy2DAsync(packed_out, stride * 2, base_row(cur), pitch, width, N,
-                                                  hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            for (uint32_t t = 0; t < N; t++)  // only words below a row's length are defined on the device
-                memset(packed_out + t * stride + lens[t], 0, (size_t)(stride - lens[t]) * 2);
-        }
+        if (packed_out && stride)
+            if (int rc = copy_rows_out(h, base_row(cur), N, lens, packed_out, stride)) return rc;
         if (lens_out) memcpy(lens_out, lens, N * sizeof(uint32_t));
         if (n) *n = (uint32_t)std::min<uint64_t>(rep.rounds, 0xFFFFFFFFu);
         if (report) *report = rep;
