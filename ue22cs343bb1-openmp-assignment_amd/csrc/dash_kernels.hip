@@ -67,11 +67,17 @@ static_assert(DASH_WCHUNK_CS8 == 2 || DASH_WCHUNK_CS8 == 4, "window chunk");
 #ifndef DASH_WAVES_PER_EU
 #define DASH_WAVES_PER_EU 0
 #endif
+#ifndef DASH_LINE_FIELD
+#define DASH_LINE_FIELD 1          // 0: the CACHE_SIZE 4 lockstep kernels derive the line state from the type (A/B builds)
+#endif
 
 // message word (ref `message`, :70-79, 20 B -> 4 B):
 //   [3:0] type  [6:4] sender  [7] dirState == S (REPLY_RD)  [14:8] address
 //   [15] the sender's reply-table flag (ignored)  [23:16] value | bitVector
 //   [27:24] ignored  [30:28] secondReceiver  [31] zero (secondReceiver is one shift)
+// The lockstep kernels of CACHE_SIZE 4 (LINE_FIELD in sim_kernel) use two of the ignored bits:
+//   [25:24] the cacheLineState the receiver's line takes if the receiver's line condition holds
+//   (set by the sender from its constant tables; bit 7 is not read there)
 __device__ __forceinline__ uint32_t mk(uint32_t type, uint32_t sender, uint32_t addr,
                                        uint32_t val, uint32_t sr, uint32_t ds_s) {
     return type | (sender << 4) | (ds_s << 7) | (addr << 8) | (val << 16) | (sr << 28);
@@ -240,6 +246,12 @@ void sim_kernel(const SimArgs a) {
     // EM entry with an empty bitVector: the state is unreachable (the oracle keeps
     // the check). Every other instantiation keeps the guard, byte for byte.
     constexpr bool NO_CTZ0 = MODE == 0 && CS == 4;
+    // The same kernels take a line's new state from the message word (bits 25..24):
+    // for every type it is a constant of the type -- REPLY_RD's by the directory state its sender
+    // reads -- so the sender's constant tables carry it and the receiver keeps one condition
+    // (mLine) and one select instead of four of each. Every other instantiation keeps today's word.
+    constexpr bool LINE_FIELD = DASH_LINE_FIELD && MODE == 0 && CS == 4;
+    constexpr uint32_t FLD = 24;  // the field's low bit
     using L = Lds<P, CS, RING>;
     constexpr uint32_t WCHUNK = wchunk_of<CS>();
     using wchunk_t = typename std::conditional<WCHUNK == 4, uint2, uint32_t>::type;
@@ -359,7 +371,10 @@ void sim_kernel(const SimArgs a) {
 
     // eviction notice (ref :767-804), sender part by the line state: EVICT_MODIFIED for M,
     // EVICT_SHARED otherwise; byte k of evb is the first message byte for line state k
-    const uint32_t evb = (T_EMOD | (t << 4)) | (T_ES | (t << 4)) * 0x01010100u;
+    // LINE_FIELD: byte 3 (line state I: never evicted) is the notice's byte 3 instead, line state E
+    // in the field -- what the home's own line takes when the home is the last sharer (ref :586)
+    const uint32_t evb = LINE_FIELD ? (T_EMOD | (t << 4)) | (T_ES | (t << 4)) * 0x00010100u | ((uint32_t)ST_E << FLD)
+                                    : (T_EMOD | (t << 4)) | (T_ES | (t << 4)) * 0x01010100u;
     // reply table, one entry per lane, read with ds_bpermute: entry (step type s, dir state
     // d) at lane 4s + d. Step types: the message types, 13 = no step, 14 / 15 = issue RD / WR.
     // Bits 3..0: the reply type (READ_REQUEST: ref :199-236, WRITE_REQUEST: :417-453, issue:
@@ -367,7 +382,7 @@ void sim_kernel(const SimArgs a) {
     // subject to the per-lane conditions applied after the lookup (ctz(0), hits). The flag
     // travels in bit 15 of the message word, which receivers ignore (addresses are 7 bits).
     constexpr uint32_t SENDS = 1u << 15;
-    const uint32_t tatab = [&] {
+    uint32_t tatab = [&] {
         const uint32_t st = lane >> 2, d = lane & 3;
         switch (st) {
         case T_RR: return SENDS | (d == D_EM ? (uint32_t)T_WBINT : (uint32_t)T_RRD | (d == D_S ? 1u << 7 : 0u));
@@ -381,6 +396,21 @@ void sim_kernel(const SimArgs a) {
         default: return 0u;
         }
     }();
+    // LINE_FIELD, bits 25..24 of an entry: the line state the reply's receiver takes, XORed with what
+    // the field source table below copies into those bits (there the reply word is tA ^ av16): nothing
+    // for most rows; the forwards (RR / WRQ at EM) copy the request's byte 0, whose low bits are its
+    // type; the flushes copy the forward's byte 3, which carries the forward's own field (S / I).
+    // REPLY_RD fills EXCLUSIVE unless the entry it was read from is SHARED (ref :252).
+    if constexpr (LINE_FIELD) {
+        const uint32_t st = lane >> 2, d = lane & 3;
+        uint32_t f = ST_M;  // REPLY_WR, REPLY_ID; the requests and UPGRADE change no line
+        if (st == T_RR) f = d == D_EM ? ST_S ^ T_RR : d == D_S ? ST_S : ST_E;
+        if (st == T_WRQ && d == D_EM) f = ST_I ^ T_WRQ;
+        if (st == T_WBINV) f = ST_M ^ ST_I;
+        if (st == T_WBINT) f = ST_S ^ ST_S;
+        if (st == T_ES) f = ST_E;
+        tatab |= f << FLD;
+    }
 
     // field source table, same index as the reply table: a v_perm selector that assembles
     // bytes 1..3 of the reply (address, value field, secondReceiver; byte 0 zero). Pool bytes:
@@ -604,16 +634,26 @@ void sim_kernel(const SimArgs a) {
         // a WR hit with its own (= the new last value)
         last_val = B(mDo) ? ins : last_val;  // value in bits 7..0 (the address above it: dropped below)
         const uint32_t fval = B(mRRD | mFLUSH) ? mv16 : last_val;
-        const mask_t mDsS = Mbit7(m);                      // REPLY_RD's dirState == S (bit 7)
+        const mask_t mDsS = LINE_FIELD ? 0 : Mbit7(m);     // REPLY_RD's dirState == S (bit 7)
         const mask_t mOwnHome = M(es_own == H);
-        const mask_t mToI = (mINV & mSame) | mWBINV;                                   // :396-398 :501
-        const mask_t mToS = mWBINT | (mRRD & mDsS) | (mFLUSH & mtSR);                  // :284 :252 :319
-        const mask_t mToE = (mES & (~mtH | (mEsOne & mOwnHome))) | (mRRD & ~mDsS);     // :558 :586 :252
-        const mask_t mToM = mRWR | mRID | (mFIA & mtSR) | mOwnHit;                     // :470 :383 :531 :709
-        uint32_t nst = B(mToM) ? (uint32_t)ST_M : lst;
-        nst = B(mToE) ? (uint32_t)ST_E : nst;
-        nst = B(mToS) ? (uint32_t)ST_S : nst;
-        nst = B(mToI) ? (uint32_t)ST_I : nst;
+        uint32_t nst;
+        if constexpr (LINE_FIELD) {
+            // the word names the state (a WR hit's is the instruction: bits 25..24 zero = ST_M); the
+            // receiver keeps the condition under which its line changes at all: a fill, a write-back,
+            // an INV of the line it holds, an EVICT_SHARED away from home or at a home that is the
+            // last sharer (:470 :383 :531 :709 :252 :284 :319 :501 :396-398 :558 :586)
+            const mask_t mLine = mFill | mWBINV | mWBINT | (mINV & mSame) | (mES & (~mtH | (mEsOne & mOwnHome)));
+            nst = B(mLine) ? (mw >> FLD) & 3u : lst;
+        } else {
+            const mask_t mToI = (mINV & mSame) | mWBINV;                                   // :396-398 :501
+            const mask_t mToS = mWBINT | (mRRD & mDsS) | (mFLUSH & mtSR);                  // :284 :252 :319
+            const mask_t mToE = (mES & (~mtH | (mEsOne & mOwnHome))) | (mRRD & ~mDsS);     // :558 :586 :252
+            const mask_t mToM = mRWR | mRID | (mFIA & mtSR) | mOwnHit;                     // :470 :383 :531 :709
+            nst = B(mToM) ? (uint32_t)ST_M : lst;
+            nst = B(mToE) ? (uint32_t)ST_E : nst;
+            nst = B(mToS) ? (uint32_t)ST_S : nst;
+            nst = B(mToI) ? (uint32_t)ST_I : nst;
+        }
         // handleCacheReplacement of the refilled line (:767-804); REPLY_WR unconditional (:467)
         const mask_t mEv = mFill & ~mlI & (mRWR | ~mSame);
 
@@ -631,11 +671,20 @@ void sim_kernel(const SimArgs a) {
         const uint32_t vsel = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((sty << 4) | (ds << 2)), (int)vstab);
         const uint32_t vpool = __builtin_amdgcn_perm(c16, e16, 0x0C010500u);  // [mem, lval, bv, 0]
         const uint32_t av16 = __builtin_amdgcn_perm(vpool, mw, vsel);  // address and value fields, in place
-        const uint32_t wA = tA | (t << 4) | av16;  // bit 15 of the address byte: ignored
+        uint32_t wA;  // bit 15 of the address byte: ignored
+        if constexpr (LINE_FIELD) {
+            // (tA ^ av16) | t << 4 in one op, where the plain word takes an or3: the same word but
+            // for bits 25..24 (the table holds the difference to the copied byte) and the ignored
+            // bit 15; the UPGRADE patch above drops the table's field: UPGRADE changes no line
+            const uint32_t t4 = t << 4;
+            asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xde" : "=v"(wA) : "v"(tA), "v"(t4), "v"(av16));
+        } else {
+            wA = tA | (t << 4) | av16;
+        }
         const uint32_t dE = laddr >> 4;
         const mask_t mInN = M(laddr < nlim);  // home node of the evicted line exists
         // one byte permute: [evb byte lst, line address, line value, 0]
-        const uint32_t wE = __builtin_amdgcn_perm(c16, evb, lst | 0x0C050400u);
+        const uint32_t wE = __builtin_amdgcn_perm(c16, evb, lst | (LINE_FIELD ? 0x03050400u : 0x0C050400u));
         const mask_t mVP = mVA | (mEv & mInN);
         const uint32_t dP = B(mVA) ? dA : dE;
         const uint32_t wP = B(mVA) ? wA : wE;
@@ -777,7 +826,7 @@ void sim_kernel(const SimArgs a) {
             for (uint32_t im = im0; im != 0; im &= im - 1u)
                 __hip_atomic_fetch_or(&lds[L::MQM + L::MQS * (seg + ffbl(im))], bitI, __ATOMIC_RELAXED,
                                       __HIP_MEMORY_SCOPE_WORKGROUP);
-            const uint32_t winv = mk(T_INV, t, addr, 0, 0, 0);
+            const uint32_t winv = mk(T_INV, t, addr, 0, 0, 0) | (LINE_FIELD ? (uint32_t)ST_I << FLD : 0u);
             for (uint32_t im = im0; im != 0; im &= im - 1u) {
                 const uint32_t rcv = L::MQS * (seg + ffbl(im));
                 const uint2 q = make_uint2(lds[L::MQM + rcv], lds[L::MQT + rcv]);
