@@ -7,7 +7,8 @@ instructions by encoding and unit: VOP1/VOP2/VOPC in their 32-bit forms, VOP3 (6
 encodings: three-operand ops, SGPR-mask selects and compares, modifiers), SDWA, SALU, LDS,
 VMEM, branches, waits. Counts are static, over one trip of the loop (DASH_QCHECK = 4
 rounds, unrolled) and divided by 4 per round; the rare blocks behind wave-uniform tests
-(REPLY_ID fan-out, errors) are listed apart. The dynamic per-round counts come from the
+(REPLY_ID fan-out, errors) are listed apart -- where they lie behind the loop (DASH_HOT_LAYOUT,
+tools/hot_layout.py) they are outside the counted body altogether. The dynamic per-round counts come from the
 PMC run (profiles/pmc_uniform.json) for comparison.
 
 VALU rate classes come from tools/micro/valu_ops.hip (profiles/r01/micro/valu_ops.txt):

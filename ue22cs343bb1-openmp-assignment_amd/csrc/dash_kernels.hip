@@ -70,6 +70,10 @@ static_assert(DASH_WCHUNK_CS8 == 2 || DASH_WCHUNK_CS8 == 4, "window chunk");
 #ifndef DASH_LINE_FIELD
 #define DASH_LINE_FIELD 1          // 0: the CACHE_SIZE 4 lockstep kernels derive the line state from the type (A/B builds)
 #endif
+// Code layout of the CACHE_SIZE 4 lockstep kernels' round loop (A/B builds):
+#ifndef DASH_HOT_LAYOUT
+#define DASH_HOT_LAYOUT 1          // 1: the cold blocks of the round and of the trip start lie behind the loop
+#endif
 
 // message word (ref `message`, :70-79, 20 B -> 4 B):
 //   [3:0] type  [6:4] sender  [7] dirState == S (REPLY_RD)  [14:8] address
@@ -214,6 +218,9 @@ __device__ __forceinline__ mask_t Mbit15(uint32_t v) {
 }
 // keeps a rarely taken branch a branch (no if-conversion onto the common path)
 #define COLD() asm volatile("" ::: "memory")
+// a COLD() block's test: where `hot` (a constant) holds, the block is also laid out of line, so the
+// common path falls through a not-taken branch; elsewhere the test is the plain one
+#define RARE(hot, c) ((hot) ? __builtin_expect((c), 0) : (c))
 
 // MODE: 0 = the fast kernel, every node steps, lowest sender first; the rarely used run
 // options get instantiations of their own, so neither they nor their kernel arguments cost
@@ -252,6 +259,9 @@ void sim_kernel(const SimArgs a) {
     // (mLine) and one select instead of four of each. Every other instantiation keeps today's word.
     constexpr bool LINE_FIELD = DASH_LINE_FIELD && MODE == 0 && CS == 4;
     constexpr uint32_t FLD = 24;  // the field's low bit
+    // The same kernels keep the round loop's common path free of taken branches: every rare block
+    // (OOB accounting, REPLY_ID fan-out, round cap, overflow stop) is placed behind the loop
+    constexpr bool HOT = DASH_HOT_LAYOUT && MODE == 0 && CS == 4;
     using L = Lds<P, CS, RING>;
     constexpr uint32_t WCHUNK = wchunk_of<CS>();
     using wchunk_t = typename std::conditional<WCHUNK == 4, uint2, uint32_t>::type;
@@ -695,7 +705,7 @@ void sim_kernel(const SimArgs a) {
         // waitingForReply, and so do FLUSH and FLUSH_INVACK at any receiver (:254,473,386,322,535)
         wmask = (mVA & mDo) | (wmask & ~(mRRD | mRWR | mRID | mFLUSH | mFIA));
         const mask_t mOob = mEv & ~mInN;  // ref UB: messageBuffers[15] -> drop + flag
-        if ((mOob | mCtz0) != 0) {        // rare: one wave-uniform test keeps it off the common path
+        if (RARE(HOT, (mOob | mCtz0) != 0)) {  // rare: one wave-uniform test keeps it off the common path
             COLD();
             err |= (B(mOob) ? DASH_ERR_OOB_D : 0u) | (B(mCtz0) ? DASH_ERR_CTZ0_D : 0u);
             drops += (B(mOob) ? 1u : 0u) + (B(mCtz0) ? 1u : 0u);
@@ -790,7 +800,7 @@ void sim_kernel(const SimArgs a) {
         }
         if (B(xVP))
             __hip_atomic_fetch_or(&lds[L::MQM + L::MQS * (seg + xdP)], bitP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (B(xVB))
+        if (HOT ? __builtin_expect(B(xVB), 1) : B(xVB))  // HOT: stays inline (live in most wave-rounds)
             __hip_atomic_fetch_or(&lds[L::MQM + L::MQS * (seg + msr)], bitB, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         auto place = [&](mask_t v, uint32_t d, uint32_t bit, uint32_t w) {
             const uint32_t rcv = L::MQS * (seg + d);
@@ -819,7 +829,7 @@ void sim_kernel(const SimArgs a) {
         // receivers (round 5: no exec test per lane and no capacity mask per store inside them;
         // at CACHE_SIZE 16, where 45 % of wave-rounds enter this block, 3.5 % less kernel time,
         // DESIGN.md §3.2)
-        if (xRID != 0) {
+        if (RARE(HOT, xRID != 0)) {
             COLD();
             // a lane without a REPLY_ID has no receivers
             const uint32_t im0 = B(xRID) ? (mv16 & rcv_all) : 0u;
@@ -865,7 +875,7 @@ void sim_kernel(const SimArgs a) {
     // the round cap is a multiple of WCHUNK (dash_create rounds it up), so it can only
     // fall on the first round of a WCHUNK block
     auto cap_check = [&](const uint32_t r0, mask_t& mMsg, mask_t& mIss) __attribute__((always_inline)) {
-        if (M(r0 == cap) != 0) {  // wave-uniform: every system still active has run `cap` rounds
+        if (RARE(HOT, M(r0 == cap) != 0)) {  // wave-uniform: every system still active has run `cap` rounds
             COLD();
             const bool kill = ((uint32_t)((mMsg | mIss | held()) >> seg) & SEGMASK) != 0;
             const mask_t mKill = M(kill);
@@ -922,7 +932,7 @@ void sim_kernel(const SimArgs a) {
         // re-simulated from scratch at the next depth, its results here are void
         if (!FINAL) {
             const mask_t ovf = M(maxd > RING * SLOT);
-            if (ovf != 0) {
+            if (RARE(HOT, ovf != 0)) {
                 COLD();
                 const bool stop = ((uint32_t)(ovf >> seg) & SEGMASK) != 0;
                 const mask_t mStop = M(stop);
