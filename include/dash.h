@@ -89,6 +89,7 @@ enum dash_txn {
                                         system's outcome on its own, without grouping equal keys of a wave */
 #define DASH_TEST_INSERT_GROUPS 64u   /* likewise: every distinct key of a wave is inserted as a group, however
                                         many there are (the default groups the first few) */
+/* testing only as well: dash_test_write_states, declared after dash_read_state */
 
 typedef struct dash_cfg {
     uint32_t num_procs;   /* NUM_PROCS (ref :6): 4 or 8 */
@@ -297,6 +298,17 @@ int dash_explore_micro(dash_t *h, uint64_t src, uint64_t first_seed, uint64_t nu
                        dash_outcome *out, uint32_t cap, uint32_t *n);
 int dash_run(dash_t *h, dash_stats *stats);
 int dash_read_state(dash_t *h, uint64_t sys, dash_node_state *out /* [num_procs] */);
+/* Testing only: overwrite the kept final states of systems [first, first + count) with hand-built ones,
+   so that dash_check_coherence can be given states no run produces. The exact inverse of
+   dash_read_state's unpacking: a directory word is memory | dir_bitvector << 8 | (dir_state & 3) << 16,
+   a line word cache_addr | cache_value << 8 | (cache_state & 3) << 16; lines at or past cache_size are
+   ignored. One copy on the handle's stream. DASH_ESTATE without DASH_KEEP_STATE or before a completed
+   dash_run; DASH_EINVAL on a range outside the batch (an empty window at the end is inside). The
+   coherence records become invalid: dash_read_coherence refuses until the next dash_check_coherence.
+   Digests, rounds, error words, histograms, event log and metrics stay the run's and no longer
+   describe the state. */
+int dash_test_write_states(dash_t *h, uint64_t first, uint64_t count,
+                           const dash_node_state *nodes /* [count * num_procs] */);
 int dash_read_results(dash_t *h, uint64_t first, uint64_t count, uint64_t *digests,
                       uint32_t *rounds, uint32_t *errors);
 int dash_read_hist(dash_t *h, uint64_t sys, uint32_t *hist /* [DASH_NUM_TXN] */);

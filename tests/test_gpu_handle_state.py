@@ -1,6 +1,7 @@
 """The handle's state rules, call by call: after every call that loads traces, changes the schedule,
 runs, computes or searches, which reads work and which refuse (DashError with ESTATE), what
-read_traces returns, and that the next run() follows the schedule source the call left behind.
+read_traces returns, and that the next run() follows the schedule source the call left behind. The
+testing-only write_states is in the table too: it voids the coherence records alone.
 
 One table per handle shape: 50 systems (a partial last wave) of 4 nodes, and of 3 (lanes per system !=
 nodes: the staged load and read-back path), cache_size 4, max_instr 32, keep_state, an event log of 64
@@ -60,6 +61,10 @@ def fill(dash, eng):
     return eng.read_results()[0]
 
 
+def state_bytes(dash, nodes):
+    return [bytes(getattr(s, f)) for s in nodes for f, _ in dash.NodeState._fields_]
+
+
 def loaded_form(tr):
     """Traces as the device keeps them: a read carries value 0."""
     return np.where(tr & 0x8000, tr, tr & 0xFF00).astype(np.uint16)
@@ -110,8 +115,30 @@ def test_state_after_every_call(dash, N, tmp_path):
         eng.run()
         assert reads(dash, eng) == RAN
         fill(dash, eng)
+
+        # ---- write_states (testing only): voids the coherence records alone, and read_state returns
+        # what was written; the next run puts the run's state back
+        ran_state = eng.read_state(S - 1)
+        st = eng.read_state(S - 1)
+        st[N - 1].cache_addr[CS - 1], st[N - 1].cache_value[CS - 1], st[N - 1].cache_state[CS - 1] = 0x05, 9, 2
+        st[0].dir_state[5], st[0].dir_bitvector[5] = 3, 0x81
+        results = [a.copy() for a in eng.read_results()]
+        eng.write_states(S - 1, [st])
+        assert reads(dash, eng) == ALL - {"read_coherence"}
+        assert state_bytes(dash, eng.read_state(S - 1)) == state_bytes(dash, st) != state_bytes(dash, ran_state)
+        assert all(np.array_equal(a, b) for a, b in zip(results, eng.read_results()))
+        eng.check_coherence()
+        assert reads(dash, eng) == ALL
+        eng.run()
+        assert reads(dash, eng) == RAN
+        assert state_bytes(dash, eng.read_state(S - 1)) == state_bytes(dash, ran_state)
+        fill(dash, eng)
+
         eng.generate(0x5EED, M)
         assert reads(dash, eng) == NONE
+        with pytest.raises(dash.DashError) as refused:
+            eng.write_states(0, [st])
+        assert refused.value.code == dash.ESTATE
         same_traces(eng, G, G_ln)
 
         # ---- the loads

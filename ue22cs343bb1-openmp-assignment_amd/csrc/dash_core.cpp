@@ -414,6 +414,35 @@ int dash_read_state(dash_t* h, uint64_t sys, dash_node_state* out) {
     });
 }
 
+// testing only: dash_read_state's unpacking, inverted, over systems [first, first + count)
+int dash_test_write_states(dash_t* h, uint64_t first, uint64_t count, const dash_node_state* nodes) {
+    return guarded(h, "dash_test_write_states", [&]() -> int {
+        if (!h || (!nodes && count)) return DASH_EINVAL;
+        if (!h->ran) return fail(h, DASH_ESTATE, "dash_run has not completed");
+        if (!h->d_state) return fail(h, DASH_ESTATE, "created without DASH_KEEP_STATE");
+        if (first + count > h->cfg.num_systems || first + count < first)
+            return fail(h, DASH_EINVAL, "range out of bounds");
+        const uint32_t N = h->cfg.num_procs, CS = h->cfg.cache_size, W = 16 + CS;
+        std::vector<uint32_t> w((size_t)count * N * W);
+        for (uint64_t k = 0; k < count * N; k++) {
+            const dash_node_state* s = &nodes[k];
+            uint32_t* o = &w[(size_t)k * W];
+            for (uint32_t b = 0; b < 16; b++)
+                o[b] = s->memory[b] | (uint32_t)s->dir_bitvector[b] << 8 | (uint32_t)(s->dir_state[b] & 3) << 16;
+            for (uint32_t i = 0; i < CS; i++)
+                o[16 + i] = s->cache_addr[i] | (uint32_t)s->cache_value[i] << 8 | (uint32_t)(s->cache_state[i] & 3) << 16;
+        }
+        h->coh.valid = false;  // the records are of the states that were
+        HIPCHK(h, hipSetDevice(h->cfg.device));
+        if (count) {
+            HIPCHK(h, hipMemcpyAsync(h->d_state + first * N * W, w.data(), w.size() * 4, hipMemcpyHostToDevice,
+                                     h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));  // w is pageable and leaves scope
+        }
+        return DASH_OK;
+    });
+}
+
 int dash_read_hist(dash_t* h, uint64_t sys, uint32_t* hist) {
     if (!h || !hist) return DASH_EINVAL;
     if (!h->ran) return fail(h, DASH_ESTATE, "dash_run has not completed");

@@ -26,6 +26,8 @@ libdash:
     Engine.check_coherence()       -> the coherence invariants of every final state, checked on the GPU
                                       (read_coherence returns the records; check_outcomes classifies
                                       an explore's outcomes; check_states is the same on the host)
+    Engine.write_states(first, l)  -> testing only: hand-built states in place of the run's, for
+                                      check_coherence (dash_test_write_states)
     dump_node(state, node)         -> printProcessorState bytes (:868-902)
     simulate_dir(dir, out_dir)     -> main() end to end
 
@@ -78,7 +80,7 @@ EXPORTS = ("dash_create", "dash_destroy", "dash_last_error", "dash_load_traces",
            "dash_set_micro_seeds", "dash_read_micro_acts", "dash_explore_micro", "dash_compute_metrics",
            "dash_read_metrics", "dash_check_states", "dash_check_coherence", "dash_read_coherence",
            "dash_check_outcomes", "dash_explore_sources", "dash_explore_assign", "dash_shrink",
-           "dash_shrink_candidate", "dash_write_dir")
+           "dash_shrink_candidate", "dash_write_dir", "dash_test_write_states")
 TEXT_TILE = 4096  # DASH_TEXT_TILE: bytes per tile of the device text parser
 SIT_OUT = 0xFF
 MICRO_STEP, MICRO_SEND = 0, 1  # dash_set_micro_schedule actions
@@ -254,6 +256,7 @@ def lib() -> ctypes.CDLL:
         "dash_probe_box": (i32, [i32, ctypes.POINTER(BoxProbe)]),
         "dash_run": (i32, [vp, ctypes.POINTER(Stats)]),
         "dash_read_state": (i32, [vp, u64, ctypes.POINTER(NodeState)]),
+        "dash_test_write_states": (i32, [vp, u64, u64, ctypes.POINTER(NodeState)]),
         "dash_read_results": (i32, [vp, u64, u64, vp, vp, vp]),
         "dash_read_hist": (i32, [vp, u64, vp]),
         "dash_stream": (vp, [vp]),
@@ -778,6 +781,21 @@ class Engine:
         arr = (NodeState * self.num_procs)()
         _check(lib().dash_read_state(self.h, sys, arr), "dash_read_state", self.h)
         return list(arr)
+
+    def write_states(self, first: int, systems):
+        """dash_test_write_states (testing only): overwrite the kept states of systems first ..
+        first + len(systems) - 1; systems is a list of lists of num_procs node states (any objects
+        with dash_node_state's fields). The coherence records become invalid; everything else the
+        run left (digests, rounds, errors, histograms, events, metrics) stays and no longer
+        describes the state."""
+        arr = (NodeState * max(len(systems) * self.num_procs, 1))()
+        for k, nodes in enumerate(systems):
+            if len(nodes) != self.num_procs:
+                raise ValueError("write_states: a system needs num_procs node states")
+            for t, s in enumerate(nodes):
+                for name, _ in NodeState._fields_:
+                    getattr(arr[k * self.num_procs + t], name)[:] = list(getattr(s, name))
+        _check(lib().dash_test_write_states(self.h, first, len(systems), arr), "dash_test_write_states", self.h)
 
     def read_hist(self, sys: int) -> np.ndarray:
         h = np.zeros(NUM_TXN, dtype=np.uint32)
