@@ -552,6 +552,74 @@ typedef struct dash_shrink_report {
 int dash_shrink(dash_t *h, uint64_t src, uint64_t seed, const dash_shrink_goal *goal,
                 uint16_t *packed_out /* [num_procs][stride] or NULL */, uint64_t stride, uint32_t *lens_out,
                 dash_shrink_step *steps, uint32_t cap, uint32_t *n, dash_shrink_report *report);
+
+/* ---- shrinking many systems side by side (csrc/dash_shrink_many.hip) ----
+   What dash_explore_sources returns, turned into reproducers in one call: a list of jobs (source system,
+   round-schedule seed, goal) is shrunk in lock-step rounds, the handle's systems dealt out over the
+   candidates of all jobs that are still shrinking. The rule, stated once:
+
+   Per job, candidates, deletion, goal, winner and stopping are dash_shrink's (above), and every variant of
+   job i runs the seeded round schedule jobs[i].seed (0 = lockstep). For every job with status
+   DASH_SHRINK_MINIMAL its steps, final trace set, lengths, rounds, variants, instr_before and instr_after
+   equal those of dash_shrink(h, src, seed, &goal, ...) on its own. Two jobs may name the same src: every
+   job's source is copied into a base row of its own before the batch is overwritten.
+
+   Before round 0, with J = num_jobs and S = cfg.num_systems: system k becomes a copy of the source of job
+   k % J, cleared past its lengths, under that job's seed; one run and one coherence launch follow.
+   src_coh_bits and src_errors of every job are those of system i < J. A job whose source does not pass
+   its own goal gets status DASH_SHRINK_UNMET: it is left as it is, with 0 rounds and 0 variants, and the
+   call goes on.
+
+   A round: all jobs advance one round together. C_i is the candidate count of job i's current base; it
+   is 0 for a job that is UNMET and for a job that has stopped, and a job stops in the round in which none
+   of its candidates passed. P_i = C_0 + ... + C_(i-1), T = P_J. The round has ceil(T / S) sub-passes. In
+   sub-pass p system k has the global index g = p * S + k:
+     - if g < T it holds candidate g - P_i of the job i with P_i <= g < P_(i+1), under job i's seed, and
+       it is counted;
+     - otherwise it holds the unchanged base of job k % J under that job's seed, and it is not counted.
+   After the round's last sub-pass every job with a passing candidate takes its winner as its new base, and
+   C_i is added to the variants of every job that had candidates, its last (failing) round included. The
+   call ends at the first round with T == 0.
+
+   dash_shrink_assign (below) is this assignment as pure host code; the device uses the same arithmetic,
+   many_assign in csrc/dash_shrink_many.h.
+
+   Afterwards system k holds the final set of job k % J (the minimal set, or the untouched source of an
+   UNMET job) and has run it once more under that job's seed, with its coherence records in place:
+   dash_read_traces, dash_read_state, dash_dump_system, dash_read_coherence and dash_read_results work on
+   it; on a seeded handle the seeds stay set.
+   Results, each optional: job i's final set into packed_out[(i * num_procs + node) * stride ..] (the rest
+   of a row is zeroed) and lens_out[i * num_procs + node]; its first step_cap winners into
+   steps[i * step_cap ..], results[i].rounds saying how many there were; results[i]; *report.
+
+   DASH_ESTATE, as for dash_shrink: created without DASH_KEEP_STATE, no traces loaded, the handle follows
+   a micro-step table, a job with seed != 0 on a handle created with schedule_seed == 0. DASH_EINVAL:
+   jobs == NULL; num_jobs 0, above cfg.num_systems or above DASH_SHRINK_MAX_JOBS; a src out of range; a
+   goal with no bit in coh_all or err_all (dash_last_error names the job); packed_out with a stride below
+   the longest source trace of any job; steps == NULL with step_cap != 0. DASH_ENOMEM when the base rows
+   do not fit: the call keeps two system rows per job on the device. */
+#define DASH_SHRINK_MAX_JOBS 65536u
+#define DASH_SHRINK_MINIMAL 0u  /* cut down to a 1-minimal set (possibly in 0 rounds) */
+#define DASH_SHRINK_UNMET   1u  /* the source does not meet its own goal: left as it is, 0 rounds, 0 variants */
+typedef struct dash_shrink_job { uint64_t src, seed; dash_shrink_goal goal; } dash_shrink_job;
+typedef struct dash_shrink_result {
+    uint32_t status, rounds;              /* rounds: winners applied */
+    uint32_t instr_before, instr_after;
+    uint64_t variants;                    /* counted candidates of this job, its last (failing) round included */
+    uint32_t src_coh_bits, src_errors;    /* the source's own record and error word under the job's seed */
+} dash_shrink_result;
+typedef struct dash_shrink_many_report {
+    uint64_t jobs, minimal, unmet;
+    uint64_t rounds;                      /* lock-step rounds of the call = the largest job's rounds + 1, 0 if no job is active */
+    uint64_t passes, variants, instr_before, instr_after; /* passes: dash_run calls = 2 + the rounds' sub-passes;
+                                                             the others: sums over the jobs */
+    double sim_ms, gen_ms, select_ms;     /* as dash_shrink_report */
+} dash_shrink_many_report;
+int dash_shrink_many(dash_t *h, const dash_shrink_job *jobs, uint64_t num_jobs,
+                     uint16_t *packed_out /* [num_jobs][num_procs][stride] or NULL */, uint64_t stride,
+                     uint32_t *lens_out /* [num_jobs][num_procs] or NULL */,
+                     dash_shrink_step *steps /* [num_jobs][step_cap] or NULL */, uint32_t step_cap,
+                     dash_shrink_result *results /* [num_jobs] or NULL */, dash_shrink_many_report *report);
 /* HIP stream the engine launches on (hipStream_t as void*) */
 void *dash_stream(dash_t *h);
 
@@ -601,6 +669,14 @@ int dash_explore_assign(uint64_t S, uint64_t G, uint64_t K, uint64_t F, uint64_t
    dash_shrink, above). Returns C >= 0, or DASH_EINVAL. Pure host code. */
 int dash_shrink_candidate(const uint32_t *lens, uint32_t num_procs, uint64_t c,
                           uint32_t *node, uint32_t *start, uint32_t *count);
+/* What system k of sub-pass `pass` of a dash_shrink_many round holds, for jobs with cands[0 .. J)
+   candidates on a handle of S systems (the rule is stated with dash_shrink_many, above): *counted, and
+   for a counted system *job and *cand (its index within that job); for an uncounted one *job = k % J and
+   *cand = 0. Each output is optional. DASH_EINVAL for cands == NULL, J == 0, J above S or above
+   DASH_SHRINK_MAX_JOBS, a count of 2^32 or more, k >= S and pass >= ceil(T / S) (so every pass when
+   T == 0). Pure host code. */
+int dash_shrink_assign(const uint64_t *cands /* [J] */, uint64_t J, uint64_t S, uint64_t pass, uint64_t k,
+                       uint64_t *job, uint64_t *cand, int *counted);
 /* One trace set as a trace directory: out_dir/core_<n>.txt for n < num_procs (out_dir is created if
    missing), node n's lens[n] words of packed[n * stride ..] as the fixtures write them, "RD 0x3C" and
    "WR 0x00 110", one per line. dash_parse_core_file reads back the same words (an RD's value bits are

@@ -61,6 +61,17 @@
  *       one line "shrink node= start= count= candidates=" per round and a last line "shrunk
  *       instr=<before>-><after> rounds= variants= bits=0x..", writes OUTDIR/core_<n>.txt and no dumps; a
  *       coherent directory prints "shrink: nothing to shrink (coherent)" and writes nothing
+ *   --shrink OUTDIR --sources FILE   the same for several directories in one call (dash_shrink_many):
+ *       <test_directory> is source 0, FILE lists the others; every incoherent one is a job, all jobs are
+ *       shrunk side by side, each to where --shrink alone takes it. Prints per job its lines "shrink
+ *       source=<i> node= start= count= candidates=" and "shrunk source=<i> instr=a->b rounds= variants=
+ *       bits=0x..", writes OUTDIR/<i>/core_<n>.txt, prints "source <i>: nothing to shrink (coherent)" for a
+ *       coherent directory and a last line "shrunk sources= minimal= coherent= distinct=" (distinct: the
+ *       different minimal trace sets)
+ *   --explore K --coherence --shrink OUTDIR   the outcome lines of --explore K --coherence, then one job per
+ *       incoherent outcome i of that list: the directory under the outcome's witness seed, with the lowest
+ *       bit of the outcome's record as the goal. The same lines with "source=<i> seed=<witness>":
+ *       `OUTDIR/<i> --schedule <witness>` replays the reproducer
  *   --sources FILE    with --explore / --explore-micro: several trace directories in one call
  *       (dash_explore_sources). <test_directory> is source 0, FILE lists the others, one per line; K
  *       schedules of every source run side by side in the batch and their outcomes are merged and
@@ -76,6 +87,7 @@
  *   --digests FILE      "system digest rounds errors" for every system
  */
 #define _POSIX_C_SOURCE 200809L
+#include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -524,10 +536,9 @@ static int shrink_dir(const char *dir, unsigned n, unsigned cs, unsigned m, int 
     return rc;
 }
 
-/* --explore K / --explore-micro K with --sources FILE: the outcomes of several trace directories in one
-   call (dash_explore_sources). dir is source 0; FILE lists the others, one per line. */
-static int explore_sources_dirs(const char *dir, const char *list, unsigned n, unsigned cs, unsigned m, int dev,
-                                unsigned long long k, unsigned long long s0, const uint64_t *weights, int coherence) {
+/* dir, then the directories that the file `list` names, one per line: (*dirs)[0 .. *g), each the caller's to
+   free; what could not be read is named on stderr */
+static int dir_list_read(const char *dir, const char *list, unsigned n, char ***dirs_out, size_t *g_out) {
     FILE *f = fopen(list, "r");
     if (!f || n < 1 || n > DASH_MAX_PROCS) {
         fprintf(stderr, "Error: could not open %s\n", list);
@@ -549,6 +560,24 @@ static int explore_sources_dirs(const char *dir, const char *list, unsigned n, u
         if (rc == DASH_OK && !(dirs[g++] = strdup(line))) rc = DASH_ENOMEM;
     }
     fclose(f);
+    *dirs_out = dirs;
+    *g_out = dirs ? g : 0;
+    return rc;
+}
+
+static void dir_list_free(char **dirs, size_t g) {
+    for (size_t s = 0; dirs && s < g; s++) free(dirs[s]);
+    free(dirs);
+}
+
+/* --explore K / --explore-micro K with --sources FILE: the outcomes of several trace directories in one
+   call (dash_explore_sources). dir is source 0; FILE lists the others, one per line. */
+static int explore_sources_dirs(const char *dir, const char *list, unsigned n, unsigned cs, unsigned m, int dev,
+                                unsigned long long k, unsigned long long s0, const uint64_t *weights, int coherence) {
+    char **dirs = NULL;
+    size_t g = 0;
+    int rc = dir_list_read(dir, list, n, &dirs, &g);
+    if (!dirs) return rc;
     /* a handle of up to 65,536 systems, at least one per source; any seeded handle: every system gets a
        seed of its own; the outcomes are classified from the final states of the passes */
     batch b = {0};
@@ -577,8 +606,191 @@ static int explore_sources_dirs(const char *dir, const char *list, unsigned n, u
     if (rc != DASH_OK && h) fprintf(stderr, "%s\n", dash_last_error(h));
     dash_destroy(h);
     batch_free(&b);
-    for (size_t s = 0; dirs && s < g; s++) free(dirs[s]);
-    free(dirs);
+    dir_list_free(dirs, g);
+    return rc;
+}
+
+/* what shrink_jobs_out compares: the jobs' final sets, as dash_shrink_many returned them */
+static struct {
+    const uint16_t *tr;
+    const uint32_t *lens;
+    size_t row, n;
+} set_cmp_ctx;
+
+static int set_cmp(const void *a, const void *b) {
+    const size_t i = *(const size_t *)a, j = *(const size_t *)b;
+    const int c = memcmp(set_cmp_ctx.lens + i * set_cmp_ctx.n, set_cmp_ctx.lens + j * set_cmp_ctx.n,
+                         set_cmp_ctx.n * sizeof *set_cmp_ctx.lens);
+    return c ? c : memcmp(set_cmp_ctx.tr + i * set_cmp_ctx.row, set_cmp_ctx.tr + j * set_cmp_ctx.row,
+                          set_cmp_ctx.row * sizeof *set_cmp_ctx.tr);
+}
+
+/* The jobs shrunk side by side (dash_shrink_many) on a loaded handle: job j is shown as source label[j]
+   (with its seed when with_seed) and its minimal set goes to out_dir/<label[j]>/core_<n>.txt. Prints the
+   jobs' "shrink" and "shrunk" lines and the closing line over `sources` sources, `coherent` of which gave
+   no job. `stride` holds the longest source trace. */
+static int shrink_jobs_out(dash_t *h, const dash_shrink_job *jobs, const uint64_t *label, size_t J, unsigned n,
+                           size_t stride, uint64_t max_instr, int with_seed, size_t sources, size_t coherent,
+                           const char *out_dir) {
+    /* a job has at most as many winners as its source has instructions; the logs together stay below 256 MB */
+    uint64_t cap = max_instr ? max_instr : 1;
+    if (J && cap > (256u << 20) / (J * sizeof(dash_shrink_step))) cap = (256u << 20) / (J * sizeof(dash_shrink_step));
+    uint16_t *tr = (uint16_t *)calloc((J ? J : 1) * n * stride, sizeof *tr);
+    uint32_t *lens = (uint32_t *)calloc((J ? J : 1) * n, sizeof *lens);
+    dash_shrink_step *steps = (dash_shrink_step *)malloc((J ? J : 1) * cap * sizeof *steps);
+    dash_shrink_result *res = (dash_shrink_result *)calloc(J ? J : 1, sizeof *res);
+    size_t *order = (size_t *)malloc((J ? J : 1) * sizeof *order);
+    dash_shrink_many_report rep = {0};
+    int rc = tr && lens && steps && res && order ? DASH_OK : DASH_ENOMEM;
+    if (rc == DASH_OK && J) rc = dash_shrink_many(h, jobs, J, tr, stride, lens, steps, (uint32_t)cap, res, &rep);
+    if (rc == DASH_OK && J && mkdir(out_dir, 0755) != 0 && errno != EEXIST) rc = DASH_EIO;
+    size_t minimal = 0, distinct = 0;
+    for (size_t j = 0; rc == DASH_OK && j < J; j++) {
+        char seed[40] = "", sub[4200];
+        if (with_seed) snprintf(seed, sizeof seed, " seed=%llu", (unsigned long long)jobs[j].seed);
+        if (res[j].status != DASH_SHRINK_MINIMAL) {
+            printf("source %llu:%s does not meet the goal (bits 0x%X errors 0x%X)\n", (unsigned long long)label[j], seed,
+                   res[j].src_coh_bits, res[j].src_errors);
+            continue;
+        }
+        for (uint32_t r = 0; r < res[j].rounds && r < cap; r++) {
+            const dash_shrink_step *st = &steps[j * cap + r];
+            printf("shrink source=%llu%s node=%u start=%u count=%u candidates=%u\n", (unsigned long long)label[j], seed,
+                   st->node, st->start, st->count, st->candidates);
+        }
+        printf("shrunk source=%llu%s instr=%u->%u rounds=%u variants=%llu bits=0x%X\n", (unsigned long long)label[j], seed,
+               res[j].instr_before, res[j].instr_after, res[j].rounds, (unsigned long long)res[j].variants,
+               jobs[j].goal.coh_all);
+        snprintf(sub, sizeof sub, "%s/%llu", out_dir, (unsigned long long)label[j]);
+        rc = dash_write_dir(tr + j * n * stride, stride, lens + j * n, n, sub);
+        order[minimal++] = j;
+    }
+    if (rc == DASH_OK) { /* the different minimal sets: lengths and words */
+        set_cmp_ctx.tr = tr;
+        set_cmp_ctx.lens = lens;
+        set_cmp_ctx.row = n * stride;
+        set_cmp_ctx.n = n;
+        qsort(order, minimal, sizeof *order, set_cmp);
+        for (size_t i = 0; i < minimal; i++) distinct += i == 0 || set_cmp(&order[i - 1], &order[i]) != 0;
+        printf("shrunk sources=%zu minimal=%zu coherent=%zu distinct=%zu\n", sources, minimal, coherent, distinct);
+    } else if (rc == DASH_EIO) {
+        fprintf(stderr, "cache_simulator: could not write %s\n", out_dir);
+    }
+    free(order);
+    free(res);
+    free(steps);
+    free(lens);
+    free(tr);
+    return rc;
+}
+
+/* the candidates of the first round over systems [0, g) of a batch, and their longest set in instructions */
+static uint64_t batch_candidates(const batch *b, size_t g, unsigned n, uint64_t *max_instr) {
+    uint64_t total = 0;
+    *max_instr = 0;
+    for (size_t s = 0; s < g; s++) {
+        uint64_t instr = 0;
+        const int C = dash_shrink_candidate(b->lens + s * n, n, 0, NULL, NULL, NULL);
+        for (unsigned t = 0; t < n; t++) instr += b->lens[s * n + t];
+        if (instr > *max_instr) *max_instr = instr;
+        total += C > 0 ? (uint64_t)C : 0;
+    }
+    return total;
+}
+
+/* --shrink OUTDIR --sources FILE: one job per incoherent directory, dir first, then those FILE lists, all
+   shrunk side by side (dash_shrink_many) under the goal shrink_dir gives a single directory */
+static int shrink_sources_dirs(const char *dir, const char *list, unsigned n, unsigned cs, unsigned m, int dev,
+                               unsigned long long sched, uint32_t bits, const char *out_dir) {
+    char **dirs = NULL;
+    size_t g = 0, J = 0;
+    int rc = dir_list_read(dir, list, n, &dirs, &g);
+    if (!dirs) return rc;
+    batch b = {0};
+    dash_t *h = NULL;
+    uint64_t max_instr = 0;
+    if (rc == DASH_OK) rc = batch_parse(&b, (const char *const *)dirs, g, n, m);
+    if (rc == DASH_OK) { /* one system per candidate of the first round, over all directories */
+        const uint64_t C = batch_candidates(&b, g, n, &max_instr);
+        rc = batch_grow(&b, C > g ? C : g, n);
+    }
+    dash_coherence *c = (dash_coherence *)calloc(g, sizeof *c);
+    uint32_t *errors = (uint32_t *)calloc(g, sizeof *errors);
+    dash_shrink_job *jobs = (dash_shrink_job *)calloc(g, sizeof *jobs);
+    uint64_t *label = (uint64_t *)calloc(g, sizeof *label);
+    if (rc == DASH_OK && (!c || !errors || !jobs || !label)) rc = DASH_ENOMEM;
+    /* every directory's own record under the schedule */
+    if (rc == DASH_OK && (rc = batch_handle(&b, n, cs, m, dev, sched, DASH_KEEP_STATE, &h)) == DASH_OK &&
+        (rc = dash_run(h, NULL)) == DASH_OK && (rc = dash_check_coherence(h, NULL)) == DASH_OK &&
+        (rc = dash_read_coherence(h, 0, g, c)) == DASH_OK)
+        rc = dash_read_results(h, 0, g, NULL, NULL, errors);
+    for (size_t s = 0; rc == DASH_OK && s < g; s++) {
+        if (c[s].bits == 0 && bits == 0) {
+            printf("source %zu: nothing to shrink (coherent)\n", s);
+            continue;
+        }
+        const dash_shrink_job job = {s, sched, {bits ? bits : c[s].bits & (0u - c[s].bits), 0, ~errors[s], 0}};
+        label[J] = s;
+        jobs[J++] = job;
+    }
+    if (rc == DASH_OK) rc = shrink_jobs_out(h, jobs, label, J, n, b.stride, max_instr, 0, g, g - J, out_dir);
+    if (rc != DASH_OK && h) fprintf(stderr, "%s\n", dash_last_error(h));
+    dash_destroy(h);
+    free(label);
+    free(jobs);
+    free(errors);
+    free(c);
+    batch_free(&b);
+    dir_list_free(dirs, g);
+    return rc;
+}
+
+/* --explore K --coherence --shrink OUTDIR: the outcomes of K seeded round schedules of one directory, as
+   --explore --coherence prints them, then one job per incoherent outcome: the directory under the outcome's
+   witness seed, shrunk side by side (dash_shrink_many) with the lowest bit of the outcome's record as the
+   goal and no error bit the outcome does not have. Job i is outcome i of the list. */
+static int explore_shrink_dir(const char *dir, unsigned n, unsigned cs, unsigned m, int dev, unsigned long long k,
+                              unsigned long long s0, const char *out_dir) {
+    batch b = {0};
+    dash_t *h = NULL;
+    uint64_t max_instr = 0;
+    int rc = batch_parse(&b, (const char *const *)&dir, 1, n, m);
+    if (rc == DASH_OK) { /* a system per schedule and per candidate of the first round, whichever is more */
+        const uint64_t C = batch_candidates(&b, 1, n, &max_instr);
+        rc = batch_grow(&b, C > k ? C : (k ? k : 1), n);
+    }
+    if (rc == DASH_OK) rc = batch_handle(&b, n, cs, m, dev, 1, DASH_KEEP_STATE, &h);
+    if (rc == DASH_OK) {
+        uint32_t total = 0, cap = 256;
+        dash_outcome *o = NULL;
+        CALL_WITH_ROOM(rc, o, cap, total, dash_explore(h, 0, s0, k, o, cap, &total));
+        dash_coherence *c = (dash_coherence *)malloc((total ? total : 1) * sizeof *c);
+        dash_shrink_job *jobs = (dash_shrink_job *)calloc(total ? total : 1, sizeof *jobs);
+        uint64_t *label = (uint64_t *)calloc(total ? total : 1, sizeof *label);
+        if (rc == DASH_OK) rc = c && jobs && label ? dash_check_outcomes(h, 0, o, total, NULL, c) : DASH_ENOMEM;
+        size_t J = 0;
+        for (uint32_t i = 0; rc == DASH_OK && i < total; i++) {
+            printf("%016llx %llu %llu %u %x %x\n", (unsigned long long)o[i].digest, (unsigned long long)o[i].count,
+                   (unsigned long long)o[i].seed, o[i].rounds, o[i].errors, c[i].bits);
+            if (c[i].bits == 0) continue;
+            const dash_shrink_job job = {0, o[i].seed, {c[i].bits & (0u - c[i].bits), 0, ~o[i].errors, 0}};
+            label[J] = i;
+            jobs[J++] = job;
+        }
+        if (rc == DASH_OK && J > b.nsys) {
+            fprintf(stderr, "cache_simulator: %zu incoherent outcomes on a batch of %llu systems\n", J,
+                    (unsigned long long)b.nsys);
+            rc = DASH_EINVAL;
+        }
+        if (rc == DASH_OK) rc = shrink_jobs_out(h, jobs, label, J, n, b.stride, max_instr, 1, total, total - J, out_dir);
+        free(label);
+        free(jobs);
+        free(c);
+        free(o);
+    }
+    if (rc != DASH_OK && h) fprintf(stderr, "%s\n", dash_last_error(h));
+    dash_destroy(h);
+    batch_free(&b);
     return rc;
 }
 
@@ -771,6 +983,7 @@ int main(int argc, char *argv[]) {
         fprintf(stderr, "       %s <test_directory> --metrics   per-node miss, invalidation and wait metrics\n", argv[0]);
         fprintf(stderr, "       %s <test_directory> --coherence   coherence invariants of the final state\n", argv[0]);
         fprintf(stderr, "       %s <test_directory> --shrink OUTDIR   a minimal trace set with the same broken state\n", argv[0]);
+        fprintf(stderr, "       %s <test_directory> --shrink OUTDIR --sources LIST   the same for many directories at once\n", argv[0]);
         return EXIT_FAILURE;
     }
     if (weights_text && parse_weights(weights_text, n, &weights) != 0) {
@@ -781,8 +994,8 @@ int main(int argc, char *argv[]) {
         fprintf(stderr, "cache_simulator: --weights goes with --micro-seed or --explore-micro\n");
         return EXIT_FAILURE;
     }
-    if (sources_file && !explore_given) {
-        fprintf(stderr, "cache_simulator: --sources goes with --explore or --explore-micro\n");
+    if (sources_file && !explore_given && !shrink_out) {
+        fprintf(stderr, "cache_simulator: --sources goes with --explore, --explore-micro or --shrink\n");
         return EXIT_FAILURE;
     }
     if (shrink_bits && !shrink_out) {
@@ -790,12 +1003,17 @@ int main(int argc, char *argv[]) {
         return EXIT_FAILURE;
     }
     if (shrink_out) {
-        if (explore_given || rounds_file || micro_file || micro_seed_given || write_rounds_file || write_micro_file ||
-            metrics || coherence) {
-            fprintf(stderr, "cache_simulator: --shrink goes with --schedule and --shrink-bits only\n");
+        /* with --explore K --coherence: one job per incoherent outcome; with --sources: one per directory */
+        const int outcomes = explore_given && !explore_micro && coherence && !sources_file && !shrink_bits;
+        if ((explore_given && !outcomes) || rounds_file || micro_file || micro_seed_given || write_rounds_file ||
+            write_micro_file || metrics || (coherence && !outcomes)) {
+            fprintf(stderr, "cache_simulator: --shrink goes with --schedule, --shrink-bits and --sources, or with "
+                            "--explore K --coherence [--schedule S0]\n");
             return EXIT_FAILURE;
         }
-        int rc = shrink_dir(dir, n, cs, m, dev, sched, shrink_bits, shrink_out);
+        int rc = outcomes       ? explore_shrink_dir(dir, n, cs, m, dev, explore, sched, shrink_out)
+                 : sources_file ? shrink_sources_dirs(dir, sources_file, n, cs, m, dev, sched, shrink_bits, shrink_out)
+                                : shrink_dir(dir, n, cs, m, dev, sched, shrink_bits, shrink_out);
         if (rc != DASH_OK) {
             const char *why = dash_last_error(NULL);
             fprintf(stderr, "cache_simulator: %s (%d)\n", why[0] ? why : "failed", rc);

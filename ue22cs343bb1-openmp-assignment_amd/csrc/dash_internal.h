@@ -1,7 +1,7 @@
 // dash_internal.h -- what the host files of libdash share: the handle, the error plumbing and
 // the helpers for device buffers and threads. Internal: not installed, not part of dash.h.
 // (dash_core.cpp, dash_sched.cpp, dash_load.cpp, dash_tools.cpp, dash_metrics.cpp,
-// dash_coherence.cpp, dash_outcomes.cpp, dash_shrink.cpp)
+// dash_coherence.cpp, dash_outcomes.cpp, dash_shrink.cpp, dash_shrink_many.cpp)
 //
 // Four mechanisms are written here once, and a new search call is written against them:
 //  * What voids results. traces_changed and schedule_changed are the only places that mark the
@@ -13,7 +13,7 @@
 //  * Stage timing. A stage_timer's events are created on first use and entered into events[], which
 //    release() destroys; mark(i) records one, add(a, b, sum) adds the time between two.
 //  * One pass of a search. run_pass for the calls that write traces or seeds on the device
-//    (dash_explore_sources, dash_shrink): the change, dash_run, its kernel time. for_each_seed_pass
+//    (dash_explore_sources, dash_shrink, dash_shrink_many): the change, dash_run, its kernel time. for_each_seed_pass
 //    for the host-driven search over seeds (dash_explore, dash_explore_micro, dash_check_outcomes).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,6 +33,8 @@
 namespace dash {
 struct OutcomeSlot;  // dash_outcomes.h
 struct OutcomeOut;
+struct ManyJob;  // dash_shrink_many.h
+struct ManyStep;
 }  // namespace dash
 
 // Stage timing with device events: mark(i) records event i on a stream, add(a, b, sum) adds the
@@ -134,6 +136,17 @@ struct dash_ctx {
         unsigned long long* d_cell = nullptr;  // the round's winner (dash::shrink_key), 0 = none
         stage_timer timer;                     // 6 marks: around the variant, select and apply launches
     } sh;
+    struct {  // dash_shrink_many (dash_shrink_many.cpp): sized by the jobs of a call, kept and reused while they fit
+        uint2* d_base = nullptr;               // [2 * jobs_cap] system rows: two per job
+        dash::ManyJob* d_jobs = nullptr;       // [jobs_cap] the jobs' records
+        uint32_t* d_words = nullptr;           // [2 * jobs_cap][DASH_MAX_PROCS] the rows' lengths, then per system its
+                                               // job, its candidate and what that deletes: [3][num_systems]
+        uint64_t* d_u64 = nullptr;             // [jobs_cap + 1] P and T, then [jobs_cap] the jobs' winner cells
+        uint64_t jobs_cap = 0;
+        dash::ManyStep* d_steps = nullptr;     // [jobs][step_cap] the device step log
+        uint64_t steps_cap = 0;
+        stage_timer timer;                     // 6 marks, as sh.timer
+    } shm;
     struct {  // device-side text ingest (dash_load.cpp): grown on first use and kept, so a repeated
               // load allocates nothing
         uint8_t* d_text = nullptr;  // text slab

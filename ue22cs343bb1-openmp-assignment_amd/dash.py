@@ -17,6 +17,9 @@ libdash:
     Engine.explore_sources(g, s0, k) -> the outcomes of g trace sets at once, merged and classified on
                                       the GPU (counts, witnesses, coherence records; explore_assign
                                       states which system runs which source and seed)
+    Engine.shrink_many(jobs)       -> many (system, seed, goal) jobs shrunk side by side in one call, each
+                                      to where Engine.shrink takes it alone (shrink_assign states how
+                                      a sub-pass's systems are dealt out)
     Engine.shrink(src, coh_all)    -> one system cut down on the GPU to a 1-minimal trace set that still
                                       ends with those coherence bits (shrink_candidate states the
                                       candidates of a round; write_dir writes the result as core_<n>.txt)
@@ -80,7 +83,8 @@ EXPORTS = ("dash_create", "dash_destroy", "dash_last_error", "dash_load_traces",
            "dash_set_micro_seeds", "dash_read_micro_acts", "dash_explore_micro", "dash_compute_metrics",
            "dash_read_metrics", "dash_check_states", "dash_check_coherence", "dash_read_coherence",
            "dash_check_outcomes", "dash_explore_sources", "dash_explore_assign", "dash_shrink",
-           "dash_shrink_candidate", "dash_write_dir", "dash_test_write_states")
+           "dash_shrink_candidate", "dash_write_dir", "dash_test_write_states", "dash_shrink_many",
+           "dash_shrink_assign")
 TEXT_TILE = 4096  # DASH_TEXT_TILE: bytes per tile of the device text parser
 SIT_OUT = 0xFF
 MICRO_STEP, MICRO_SEND = 0, 1  # dash_set_micro_schedule actions
@@ -224,6 +228,26 @@ class ShrinkReport(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+# dash_shrink_job / dash_shrink_result / dash_shrink_many_report (dash_shrink_many)
+SHRINK_MAX_JOBS = 65536
+SHRINK_MINIMAL, SHRINK_UNMET = 0, 1
+SHRINK_JOB_DTYPE = np.dtype([("src", np.uint64), ("seed", np.uint64), ("coh_all", np.uint32), ("err_all", np.uint32),
+                             ("err_none", np.uint32), ("_reserved", np.uint32)])
+SHRINK_RESULT_DTYPE = np.dtype([("status", np.uint32), ("rounds", np.uint32), ("instr_before", np.uint32),
+                                ("instr_after", np.uint32), ("variants", np.uint64), ("src_coh_bits", np.uint32),
+                                ("src_errors", np.uint32)])
+assert SHRINK_JOB_DTYPE.itemsize == 32 and SHRINK_RESULT_DTYPE.itemsize == 32
+
+
+class ShrinkManyReport(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint64) for f in ("jobs", "minimal", "unmet", "rounds", "passes", "variants",
+                                               "instr_before", "instr_after")] + \
+               [(f, ctypes.c_double) for f in ("sim_ms", "gen_ms", "select_ms")]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class Gen(ctypes.Structure):
     _fields_ = [("seed", ctypes.c_uint64), ("sys_base", ctypes.c_uint64), ("kind", ctypes.c_uint32),
                 ("locality", ctypes.c_uint32), ("len", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
@@ -305,6 +329,9 @@ def lib() -> ctypes.CDLL:
                               ctypes.POINTER(ShrinkReport)]),
         "dash_shrink_candidate": (i32, [vp, u32, u64, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32)]),
         "dash_write_dir": (i32, [vp, u64, vp, u32, ctypes.c_char_p]),
+        "dash_shrink_many": (i32, [vp, vp, u64, vp, u64, vp, vp, u32, vp, ctypes.POINTER(ShrinkManyReport)]),
+        "dash_shrink_assign": (i32, [vp, u64, u64, u64, u64, ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                     ctypes.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -484,6 +511,18 @@ def shrink_candidate(lens, c: int):
                                     ctypes.byref(count))
     _check(C if C < 0 else OK, "dash_shrink_candidate")
     return (C, node.value, start.value, count.value) if C else (0, None, None, None)
+
+
+def shrink_assign(cands, S: int, pass_: int, k: int):
+    """dash_shrink_assign: (job, cand, counted) of system k in sub-pass `pass_` of a shrink_many round whose
+    jobs have cands[i] candidates, on a handle of S systems; an uncounted system holds the base of job
+    k % len(cands)."""
+    cands = np.ascontiguousarray(cands, dtype=np.uint64)
+    assert cands.ndim == 1
+    job, cand, counted = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int()
+    _check(lib().dash_shrink_assign(cands.ctypes.data if len(cands) else None, len(cands), S, pass_, k,
+                                    ctypes.byref(job), ctypes.byref(cand), ctypes.byref(counted)), "dash_shrink_assign")
+    return job.value, cand.value, bool(counted.value)
 
 
 def write_dir(trace, lens, out_dir):
@@ -771,6 +810,30 @@ class Engine:
         _check(lib().dash_shrink(self.h, src, seed, ctypes.byref(goal), trace.ctypes.data, stride, lens.ctypes.data,
                                  steps.ctypes.data, want, ctypes.byref(n), ctypes.byref(rep)), "dash_shrink", self.h)
         return {"trace": trace, "lens": lens, "steps": steps[:min(n.value, want)], "report": rep.as_dict()}
+
+    def shrink_many(self, jobs, cap=None) -> dict:
+        """dash_shrink_many: the jobs, rows of (src, seed, coh_all, err_all, err_none), shrunk side by side
+        on the GPU, each to where Engine.shrink would take it alone. Returns dict(trace [J, num_procs,
+        max_instr] u16, lens [J, num_procs], steps: a list of SHRINK_STEP_DTYPE arrays, results: a
+        SHRINK_RESULT_DTYPE array (status SHRINK_MINIMAL or SHRINK_UNMET per job), report dict).
+        Afterwards system k holds the final set of job k % J, run and checked. cap=k keeps the first k
+        steps of every job (results["rounds"] has their number)."""
+        rows = [tuple(int(x) for x in j) for j in jobs]
+        rec = np.zeros(len(rows), dtype=SHRINK_JOB_DTYPE)
+        for i, (src, seed, coh_all, err_all, err_none) in enumerate(rows):
+            rec[i] = (src, seed, coh_all, err_all, err_none, 0)
+        J, N, stride = len(rows), self.num_procs, max(int(self.cfg.max_instr), 1)
+        trace = np.zeros((J, N, stride), dtype=np.uint16)
+        lens = np.zeros((J, N), dtype=np.uint32)
+        want = N * stride if cap is None else cap  # a job has at most as many rounds as instructions
+        steps = np.zeros((max(J, 1), max(want, 1)), dtype=SHRINK_STEP_DTYPE)
+        results = np.zeros(max(J, 1), dtype=SHRINK_RESULT_DTYPE)
+        rep = ShrinkManyReport()
+        _check(lib().dash_shrink_many(self.h, rec.ctypes.data if J else None, J, trace.ctypes.data, stride,
+                                      lens.ctypes.data, steps.ctypes.data if want else None, want, results.ctypes.data,
+                                      ctypes.byref(rep)), "dash_shrink_many", self.h)
+        return {"trace": trace, "lens": lens, "steps": [steps[i, :min(int(results["rounds"][i]), want)] for i in range(J)],
+                "results": results[:J], "report": rep.as_dict()}
 
     def run(self) -> dict:
         st = Stats()
