@@ -553,7 +553,7 @@ int dash_shrink(dash_t *h, uint64_t src, uint64_t seed, const dash_shrink_goal *
                 uint16_t *packed_out /* [num_procs][stride] or NULL */, uint64_t stride, uint32_t *lens_out,
                 dash_shrink_step *steps, uint32_t cap, uint32_t *n, dash_shrink_report *report);
 
-/* ---- shrinking many systems side by side (csrc/dash_shrink_many.hip) ----
+/* ---- shrinking many systems side by side (csrc/dash_shrink.hip) ----
    What dash_explore_sources returns, turned into reproducers in one call: a list of jobs (source system,
    round-schedule seed, goal) is shrunk in lock-step rounds, the handle's systems dealt out over the
    candidates of all jobs that are still shrinking. The rule, stated once:
@@ -582,7 +582,7 @@ int dash_shrink(dash_t *h, uint64_t src, uint64_t seed, const dash_shrink_goal *
    call ends at the first round with T == 0.
 
    dash_shrink_assign (below) is this assignment as pure host code; the device uses the same arithmetic,
-   many_assign in csrc/dash_shrink_many.h.
+   many_assign in csrc/dash_shrink.h.
 
    Afterwards system k holds the final set of job k % J (the minimal set, or the untouched source of an
    UNMET job) and has run it once more under that job's seed, with its coherence records in place:

@@ -40,13 +40,15 @@ CAP_SOURCES = {
         "constexpr uint32_t THREADS = 256;",
         "const uint64_t blocks = std::min<uint64_t>((work + THREADS - 1) / THREADS, 256ull * 64);",
     ],
-    "dash_shrink.hip": [  # launch_variants: gridDim.y <= 65,535, 1,024 (node, chunk) items per x-block
+    "dash_shrink.hip": [  # row_grid: gridDim.y <= 65,535, 1,024 (node, chunk) items per x-block
         "constexpr uint32_t THREADS = 256;",
         "constexpr uint32_t ITEMS_PER_BLOCK = 4 * THREADS;",
-        "(uint32_t)std::min<uint64_t>(a.nsys, 65535)",
+        "(uint32_t)std::min<uint64_t>(rows, 65535)",
+        # base_wchunks: a row's own share of the engine's wchunks
+        "return min(cap, (longest + 3u) / 4u + 2u);",
     ],
-    "dash_shrink.cpp": [  # write_chunks: the trace and its two refill chunks
-        "std::min<uint64_t>(h->nchunks, ((uint64_t)max_len + 3) / 4 + 2)",
+    "dash_shrink.cpp": [  # the engine's wchunks: the longest source trace and its two refill chunks
+        "std::min<uint64_t>(h->nchunks, ((uint64_t)src_max + 3) / 4 + 2)",
     ],
     "dash_coherence.hip": [  # launch_coherence: 4 waves per workgroup, at most 1,024 trips of one
         "constexpr uint32_t WAVES = 4;",
@@ -73,7 +75,7 @@ CAP_SOURCES = {
 
 GRID_STRIDE_THREADS = 256 * 64 * 256   # clear_rd, broadcast, replicate: threads of the capped grid
 MARK_THREADS = 1024 * 256              # mark_kernel's
-VARIANT_MAX_Y = 65535                  # variant_kernel: systems per y-trip
+VARIANT_MAX_Y = 65535                  # many_variant_kernel: systems per y-trip
 VARIANT_ITEMS_PER_BLOCK = 1024         # and (node, chunk) items per x-block
 COH_WAVES, COH_MAX_TRIPS = 4, 1024     # coherence_kernel
 SLAB_BYTES = 64 << 20                  # dash_load_dirs_device
@@ -91,7 +93,7 @@ def nchunks(max_instr):
 
 
 def write_chunks(max_instr, max_len):
-    """dash_shrink's chunks written per stream over a base whose longest trace is max_len."""
+    """The shrink engine's chunks written per stream over a base whose longest trace is max_len."""
     return max(1, min(nchunks(max_instr), (max_len + 3) // 4 + 2))
 
 

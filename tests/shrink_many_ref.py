@@ -1,7 +1,7 @@
 """Plain-Python twin of dash_shrink_many, written from the text of include/dash.h alone: every job is the
 twin of dash_shrink (tests/shrink_ref.py) on its own, or UNMET when its source does not pass its goal; the
 lock-step rounds' candidate counts follow from the jobs' steps; assign() is the header's rule for what a
-system of a sub-pass holds. No arithmetic shared with csrc/dash_shrink_many.h.
+system of a sub-pass holds. No arithmetic shared with csrc/dash_shrink.h.
 
 TEST INFRASTRUCTURE: used by tests/test_shrink_many_spec.py (CPU) and tests/test_gpu_shrink_many.py.
 """

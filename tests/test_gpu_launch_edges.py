@@ -1,5 +1,5 @@
 """The kernels around sim_kernel where a launch takes a second trip, block or slab: the grid-stride
-loops of clear_rd, broadcast, replicate and mark past their capped grids, variant_kernel's y-stride
+loops of clear_rd, broadcast, replicate and mark past their capped grids, many_variant_kernel's y-stride
 and second x-block, coherence_kernel's walk of several trips and its grid floor, the event log past
 byte 2^32, dash_load_dirs_device's reuse of a pinned slab, and dash_write_digests' second window.
 
@@ -213,7 +213,7 @@ def test_event_log_past_4_gib(dash, seed):
 # ---------------------------------------------------------------- 6. shrink: the y-stride
 
 def test_shrink_on_more_systems_than_grid_rows(dash):
-    """variant_kernel's gridDim.y is capped at 65,535: on 65,600 systems the last ones are written by
+    """many_variant_kernel's gridDim.y is capped at 65,535: on 65,600 systems the last ones are written by
     the y-stride only, and check_against_twin reads the last system's traces, results and record."""
     row = sr.ROWS[1]
     N_, CS_, r, seed = row
@@ -231,7 +231,7 @@ def test_shrink_on_more_systems_than_grid_rows(dash):
 # ---------------------------------------------------------------- 7. shrink: two x-blocks
 
 def test_shrink_of_long_traces(dash):
-    """8 nodes x 600 instructions: 152 chunks per stream, 1,216 (node, chunk) items, so variant_kernel
+    """8 nodes x 600 instructions: 152 chunks per stream, 1,216 (node, chunk) items, so many_variant_kernel
     runs two x-blocks per system, the second with the end of node 6 and all of node 7; 9,624
     candidates on 4,096 systems make three sub-passes in the first round. Steps, lengths and traces
     are the twin's (tests/golden/shrink_long.json, re-checked on the CPU)."""

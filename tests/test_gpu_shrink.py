@@ -138,6 +138,16 @@ def test_error_paths(dash):
         with pytest.raises(dash.DashError) as e:
             eng.shrink(k, missing)
         assert e.value.code == dash.EINVAL and "does not meet the goal" in str(e.value)
+        # what include/dash.h promises of the refusal: the batch holds copies of the source, run and checked
+        src = np.where(np.arange(M)[None, :] < lens[:, None], _tr, 0)  # zero past its lengths
+        want = oc.run_system(_tr, lens, num_procs=N, cache_size=CS, arb_seed=seed)
+        got_tr, got_ln = eng.read_traces()
+        dig, rnd, err = eng.read_results()
+        rec = eng.read_coherence()
+        for s in (0, 49):
+            assert got_ln[s].tolist() == lens.tolist() and np.array_equal(got_tr[s], src), s
+            assert (int(dig[s]), int(rnd[s]), int(err[s])) == (want.digest, want.rounds, want.errors), s
+            assert cr.record(rec[s]) == cr.check(want.node, N, CS)[0], s
         assert code(lambda: eng.shrink(k, bit, err_all=dash.ERR_OOB)) == dash.EINVAL
         # after the refusals the handle still shrinks (the refused calls left copies of the source behind)
         # cap smaller than the rounds: the first steps, and *n says how many there were

@@ -1,4 +1,4 @@
-"""dash_shrink_many (csrc/dash_shrink_many.hip, csrc/dash_shrink_many.cpp) on the GPU: many jobs (source
+"""dash_shrink_many (csrc/dash_shrink.hip, csrc/dash_shrink.cpp) on the GPU: many jobs (source
 system, seed, goal) shrunk side by side in lock-step rounds, the handle's systems dealt out over the
 candidates of all jobs that are still shrinking.
 
@@ -96,8 +96,9 @@ def test_shrink_many_equals_twin(dash, shape, S):
 
 @pytest.mark.parametrize("shape", smr.SHAPES, ids=["N%d-cs%d-r%d" % s for s in smr.SHAPES])
 def test_shrink_many_equals_shrink(dash, shape):
-    """dash_shrink on a handle of its own, job by job: the same steps and traces for a MINIMAL job, a refusal
-    for an UNMET one."""
+    """dash_shrink, the one-job case of the same engine, on a handle of its own, job by job: the same steps
+    and traces for a MINIMAL job, a refusal for an UNMET one. A job's result does not depend on which other
+    jobs share the call (both sides are pinned on the CPU twin elsewhere)."""
     N, CS, r = shape
     jobs = smr.jobs(*shape)
     with engine(dash, N, CS, 600) as eng:

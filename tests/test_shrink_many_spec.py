@@ -71,7 +71,7 @@ def test_assign_refusals(dash):
 
 
 def test_assign_arithmetic_under_host_sanitizers(tmp_path):
-    """csrc/dash_shrink_many.h's many_find_job and many_assign, compiled for the host into a stand-alone
+    """csrc/dash_shrink.h's many_find_job and many_assign, compiled for the host into a stand-alone
     program with AddressSanitizer and UBSan, against a plain loop over the jobs."""
     rocm = pathlib.Path(os.environ.get("ROCM_PATH", "/opt/rocm")) / "include"  # hip_runtime.h, for uint2
     exe = tmp_path / "shrink_many_host_check"

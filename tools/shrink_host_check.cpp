@@ -1,10 +1,10 @@
 // shrink_host_check.cpp -- test infrastructure (tests/test_shrink_spec.py builds and runs it, with the
-// host sanitizers): the variant kernel's chunk arithmetic (csrc/dash_shrink.h: shrink_decode,
+// host sanitizers): the chunk arithmetic of a written row (csrc/dash_shrink.h: shrink_decode,
 // variant_chunk) on the CPU against a plain deletion over arrays of instructions.
 //
 // For random bases in the engine's layout (node t's stream = nchunks 8-B chunks, garbage past its length)
 // every candidate of the base -- or, for long bases, an evenly spaced sample of them with the last one --
-// and the base itself (index C) are written chunk by chunk exactly as variant_kernel's loop does, and compared
+// and the base itself (index C) are written chunk by chunk exactly as write_row's loop (csrc/dash_shrink.hip) does, and compared
 // word for word with the deletion done the slow way. Streams sit in exactly-sized heap blocks, so a read
 // outside [0, nchunks) of a stream is an AddressSanitizer report.
 #include <cstdio>

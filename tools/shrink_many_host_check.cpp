@@ -1,6 +1,6 @@
 // shrink_many_host_check.cpp -- test infrastructure (tests/test_shrink_many_spec.py builds and runs it, with
-// the host sanitizers): the arithmetic dash_shrink_many's kernels share with the host
-// (csrc/dash_shrink_many.h: many_find_job, many_assign) on the CPU against a plain loop over the jobs.
+// the host sanitizers): the arithmetic the shrink engine's kernels share with the host
+// (csrc/dash_shrink.h: many_find_job, many_assign) on the CPU against a plain loop over the jobs.
 //
 // For a vector of candidate counts and a handle size S, every system of every sub-pass -- and of one
 // sub-pass past the last, where nothing is counted -- is assigned both ways (for the large vectors a sample
@@ -12,7 +12,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "dash_shrink_many.h"
+#include "dash_shrink.h"
 
 static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
 static uint64_t rnd() {

@@ -10,9 +10,10 @@ error bit, each under the goal "the lowest bit of its own record, no error bit".
 
 (a) dash_shrink_many over all jobs: a host clock around the call (it returns with the stream synchronised),
     and its report: sim_ms / gen_ms / select_ms (device events), lock-step rounds, dash_run calls, variants.
-(b) the yardstick, today's route: a loop of dash_shrink over the same jobs on the same handle, the host clock
-    around each call, summed. A call overwrites the batch, so the generator puts the sources back before
-    every call of either route; that time is kept apart (restore_s) and is in neither total.
+(b) the yardstick, the route without it: a loop of dash_shrink (the same engine, one job per call) over the
+    same jobs on the same handle, the host clock around each call, summed. A call overwrites the batch, so
+    the generator puts the sources back before every call of either route; that time is kept apart
+    (restore_s) and is in neither total.
 The two routes alternate, --reps rounds (fewer when --budget-s runs out; reps_done says how many), medians;
 every round asserts identical steps, traces and lengths, job by job. Nothing is gated: the figures go to
 --out (profiles/shrink_many.json) with the box probe. A gain is stated in spreads: (median of (b) - median

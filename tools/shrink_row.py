@@ -8,8 +8,9 @@ lowest bit of its record, no error bit", on the same handle of --systems systems
 (a) dash_shrink: a host clock around the call (it returns with the stream synchronised), and its report:
     sim_ms / gen_ms / select_ms (device events), rounds, variants, dash_run calls. Bytes the candidate
     kernel writes are computed here from the steps: per sub-pass systems x nodes x written chunks x 8 B
-    (csrc/dash_shrink.cpp: the chunks of the base's longest trace plus two); gen_ms also holds the apply
-    launches and the two copies of the base, so bytes / gen_ms understates the kernel's own rate.
+    (csrc/dash_shrink.hip, base_wchunks: the chunks of the base's longest trace plus two); gen_ms also holds
+    the apply launches and the two copies of the base, so bytes / gen_ms understates the kernel's own rate.
+    The call is the one-job case of the engine that dash_shrink_many runs.
 (b) the old route, in this tool: per round the host builds every candidate of the base into a whole-batch
     buffer (numpy; stride = the base's longest trace), then dash_load_traces, dash_run,
     dash_check_coherence, dash_read_coherence and dash_read_results per sub-pass, selection in numpy.

@@ -1,7 +1,7 @@
 // dash_internal.h -- what the host files of libdash share: the handle, the error plumbing and
 // the helpers for device buffers and threads. Internal: not installed, not part of dash.h.
 // (dash_core.cpp, dash_sched.cpp, dash_load.cpp, dash_tools.cpp, dash_metrics.cpp,
-// dash_coherence.cpp, dash_outcomes.cpp, dash_shrink.cpp, dash_shrink_many.cpp)
+// dash_coherence.cpp, dash_outcomes.cpp, dash_shrink.cpp)
 //
 // Four mechanisms are written here once, and a new search call is written against them:
 //  * What voids results. traces_changed and schedule_changed are the only places that mark the
@@ -33,7 +33,7 @@
 namespace dash {
 struct OutcomeSlot;  // dash_outcomes.h
 struct OutcomeOut;
-struct ManyJob;  // dash_shrink_many.h
+struct ManyJob;  // dash_shrink.h
 struct ManyStep;
 }  // namespace dash
 
@@ -73,7 +73,7 @@ struct dash_ctx {
         void* p;
         bool pinned;
     } owned[48] = {};
-    hipEvent_t events[24] = {};  // the stage timers' events: timer_ready enters them, release() destroys them
+    hipEvent_t events[18] = {};  // the stage timers' events: timer_ready enters them, release() destroys them
     uint2* d_trace = nullptr;
     uint32_t* d_lens = nullptr;
     uint64_t* d_digests = nullptr;
@@ -129,14 +129,7 @@ struct dash_ctx {
         unsigned long long* d_counters = nullptr;  // [dash::OC_WORDS]
         stage_timer timer;                     // 5 marks: around the kernels before / after dash_run, and after the insert
     } oc;
-    struct {  // dash_shrink (dash_shrink.cpp)
-        uint2* d_base = nullptr;               // [2] system rows: the base and the row the next one is written to
-        uint32_t* d_lens = nullptr;            // [2][DASH_MAX_PROCS] their lengths
-        uint32_t* d_count = nullptr;           // [num_systems] instructions each system's candidate deletes
-        unsigned long long* d_cell = nullptr;  // the round's winner (dash::shrink_key), 0 = none
-        stage_timer timer;                     // 6 marks: around the variant, select and apply launches
-    } sh;
-    struct {  // dash_shrink_many (dash_shrink_many.cpp): sized by the jobs of a call, kept and reused while they fit
+    struct {  // dash_shrink, dash_shrink_many (dash_shrink.cpp): sized by the jobs of a call, kept and reused while they fit
         uint2* d_base = nullptr;               // [2 * jobs_cap] system rows: two per job
         dash::ManyJob* d_jobs = nullptr;       // [jobs_cap] the jobs' records
         uint32_t* d_words = nullptr;           // [2 * jobs_cap][DASH_MAX_PROCS] the rows' lengths, then per system its
@@ -145,7 +138,7 @@ struct dash_ctx {
         uint64_t jobs_cap = 0;
         dash::ManyStep* d_steps = nullptr;     // [jobs][step_cap] the device step log
         uint64_t steps_cap = 0;
-        stage_timer timer;                     // 6 marks, as sh.timer
+        stage_timer timer;                     // 6 marks: around the variant, select and apply launches
     } shm;
     struct {  // device-side text ingest (dash_load.cpp): grown on first use and kept, so a repeated
               // load allocates nothing

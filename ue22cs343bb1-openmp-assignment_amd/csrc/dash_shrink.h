@@ -1,5 +1,7 @@
-// dash_shrink.h -- the device side of dash_shrink (dash_shrink.hip): the candidate enumeration, stated
-// once for the host and the kernels, and the launches.
+// dash_shrink.h -- the device side of the shrink engine (dash_shrink.hip), which dash_shrink_many drives
+// with many jobs and dash_shrink with one: the candidate enumeration, the deletion, the winner key and the
+// assignment of a sub-pass's systems to the jobs' candidates, stated once for the host and the kernels, the
+// per-job record the kernels keep, and the launches.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -14,8 +16,8 @@ struct ShrinkCand {
 
 // The candidate enumeration of include/dash.h (dash_shrink): by node ascending, by level j = J .. 0
 // (2^J >= lens[t] > 2^(J-1)), by block start. Returns C, the number of candidates of the base, and sets
-// `out` to candidate c when c < C (it is left alone otherwise). dash_shrink_candidate, the candidate
-// kernel and the apply kernel all decode through this one function. lens[t] <= SHRINK_MAX_LEN.
+// `out` to candidate c when c < C (it is left alone otherwise). dash_shrink_candidate, the scan, the variant
+// kernel and the apply kernels all decode through this one function. lens[t] <= SHRINK_MAX_LEN.
 __host__ __device__ inline uint64_t shrink_decode(const uint32_t* lens, uint32_t num_procs, uint64_t c, ShrinkCand& out) {
     uint64_t total = 0;  // the candidates of the nodes and levels before this one; c >= total until found
     bool found = false;
@@ -46,8 +48,8 @@ __host__ __device__ inline unsigned long long shrink_key(uint32_t count, uint64_
 }
 __host__ __device__ inline uint64_t shrink_key_candidate(unsigned long long key) { return 0xFFFFFFFFu - (uint32_t)key; }
 
-// ---- the chunk arithmetic of the variant kernel (dash_shrink.hip), host-callable so that a CPU program
-// can check it against a plain deletion ----
+// ---- the chunk arithmetic of a written row (dash_shrink.hip: write_row), host-callable so that a CPU
+// program can check it against a plain deletion ----
 
 __host__ __device__ inline uint64_t chunk_load(const uint2* p) {
     const uint2 v = *p;
@@ -84,36 +86,96 @@ __host__ __device__ inline uint64_t variant_chunk(const uint2* stream, uint32_t 
     return v;
 }
 
-enum ShrinkMode : uint32_t {
-    SHRINK_CANDIDATES = 0,  // system k := the base without candidate first + k (past C: the base itself)
-    SHRINK_COPY = 1,        // every system := the base
-    SHRINK_APPLY = 2,       // system 0 := the base without the winner in *cell; nothing when *cell == 0
+constexpr uint32_t MANY_NO_JOB = 0xFFFFFFFFu;  // a system that holds no counted candidate
+
+// The job of global candidate index g: the i < J with P[i] <= g < P[i + 1], for an exclusive prefix
+// P[0 .. J] of the jobs' candidate counts (P[0] = 0, P[J] = T) and g < T. Jobs without candidates
+// (P[i] == P[i + 1]) are never returned. A bisection: at most 17 steps for 65,536 jobs.
+__host__ __device__ inline uint64_t many_find_job(const uint64_t* P, uint64_t J, uint64_t g) {
+    uint64_t lo = 0, hi = J;  // P[lo] <= g < P[hi]
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (P[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The rule of include/dash.h (dash_shrink_many, "A round"): what system k < S of sub-pass `pass` holds.
+// Returns whether it is counted; then job and cand are the candidate's, else job = k % J and cand = 0 (the
+// unchanged base of that job). J >= 1, S >= 1.
+__host__ __device__ inline bool many_assign(const uint64_t* P, uint64_t J, uint64_t S, uint64_t pass, uint64_t k,
+                                            uint64_t& job, uint64_t& cand) {
+    const uint64_t g = pass * S + k;
+    if (g < P[J]) {
+        job = many_find_job(P, J, g);
+        cand = g - P[job];
+        return true;
+    }
+    job = k % J;
+    cand = 0;
+    return false;
+}
+
+// What the device keeps per job: the host writes src, seed and the goal, the kernels the rest.
+struct ManyJob {
+    uint64_t src, seed;
+    uint64_t variants;                    // counted candidates so far
+    uint32_t coh_all, err_all, err_none;  // the goal
+    uint32_t cur;                         // which of the job's two base rows holds its base
+    uint32_t active;                      // still shrinking: met its goal, and a candidate passed in every round so far
+    uint32_t status;                      // DASH_SHRINK_MINIMAL / DASH_SHRINK_UNMET
+    uint32_t rounds;                      // winners applied
+    uint32_t cands;                       // C_i of the round in flight (the scan writes it; 0 when not active)
+    uint32_t src_coh_bits, src_errors;    // the source's own record and error word
+};
+static_assert(sizeof(ManyJob) == 64, "one 64-B record per job");
+
+struct ManyStep {  // dash_shrink_step
+    uint32_t node, start, count, candidates;
 };
 
-// One launch of variant_kernel: `nsys` systems written from one base. All rows are in the engine's
-// lane-contiguous layout: a system is `row` consecutive 8-B chunks, node t's stream the nchunks chunks at
-// t * nchunks, four packed instructions per chunk.
-struct VariantArgs {
-    const uint2* base;          // one system row
-    const uint32_t* base_lens;  // [num_procs]
-    uint2* dst;                 // nsys rows
-    uint32_t* dst_lens;         // [nsys * num_procs]
-    uint32_t* dst_count;        // optional [nsys]: the instructions system k's candidate deletes (0: none)
-    uint64_t nsys, row, first;
+constexpr uint32_t MANY_LENS = 8;  // lengths per base row (DASH_MAX_PROCS)
+
+// Everything the kernels of a call share. Rows are in the engine's lane-contiguous layout: a system is
+// `row` consecutive 8-B chunks, node t's stream the nchunks chunks at t * nchunks, four packed instructions
+// per chunk. Job i's two base rows are rows 2 i and 2 i + 1 of base, their lengths base_lens[(2 i + r) *
+// MANY_LENS ..].
+struct ManyArgs {
+    ManyJob* jobs;             // [J]
+    uint2* base;               // [2 J] system rows
+    uint32_t* base_lens;       // [2 J][MANY_LENS]
+    uint64_t* prefix;          // [J + 1]: P, with T = P[J]
+    unsigned long long* cell;  // [J] the round's winner per job (shrink_key), 0 = none
+    ManyStep* steps;           // [J][step_cap] the first step_cap winners of every job
+    uint32_t* sys_job;         // [S] the job whose candidate system k holds, MANY_NO_JOB when it is not counted
+    uint32_t* sys_cand;        // [S] that candidate's index within its job
+    uint32_t* sys_count;       // [S] the instructions it deletes
+    uint2* trace;              // the batch: S rows
+    uint32_t* lens;            // [S * num_procs]
+    uint64_t* seeds;           // [S] per-system schedule seeds, nullptr on a handle without a schedule seed
+    const uint32_t* errors;    // [S] of the last run
+    const uint4* coh;          // [S] its coherence records
+    uint64_t J, S, row;
     uint32_t nchunks, num_procs;
-    uint32_t wchunks;           // chunks written per stream, 1 .. nchunks: covers the base's longest trace
-                                // (the simulator reads nothing past a stream's length but its two refill chunks)
-    uint32_t mode;              // ShrinkMode
-    const unsigned long long* cell;  // SHRINK_APPLY
+    uint32_t wchunks;          // chunks per stream that cover the longest source trace and its two refill chunks
+    uint32_t step_cap;
 };
-hipError_t launch_variants(const VariantArgs& a, hipStream_t s);
 
-// The goal over systems [0, counted) of a sub-pass whose system 0 holds candidate `first`: the key of every
-// passing one into *cell (one 64-bit atomicMax per wave that has any)
-hipError_t launch_select(const uint32_t* errors, const uint4* coh, const uint32_t* count, uint64_t counted,
-                         uint64_t first, uint32_t coh_all, uint32_t err_all, uint32_t err_none,
-                         unsigned long long* cell, hipStream_t s);
-// seeds[k] = seed for k < n
-hipError_t launch_fill_u64(uint64_t* seeds, uint64_t n, uint64_t seed, hipStream_t s);
+// base row 0 of every job := its source system, cleared past its lengths; the record's device fields reset
+hipError_t launch_many_init(const ManyArgs& a, hipStream_t s);
+// Round 0, after the run and the coherence launch over copies of the sources: src_coh_bits, src_errors,
+// status and active of job i from system i
+hipError_t launch_many_mark(const ManyArgs& a, hipStream_t s);
+// cands of every job, P, T, and the cells cleared: one workgroup
+hipError_t launch_many_scan(const ManyArgs& a, hipStream_t s);
+// Every system of the batch written from the base of its job: many_assign's for sub-pass `pass`, or with
+// copy the unchanged base of job k % J. Lengths, deleted count, job, candidate and seed per system.
+hipError_t launch_many_variants(const ManyArgs& a, uint64_t pass, bool copy, hipStream_t s);
+// the key of every counted system that passes its job's goal into cell[job]
+hipError_t launch_many_select(const ManyArgs& a, hipStream_t s);
+// Every job with a winner: its other base row written, then the step logged, rounds and variants added, the
+// rows flipped; a job without one stops. Two launches: no row is read after its job's `cur` has flipped.
+hipError_t launch_many_apply(const ManyArgs& a, hipStream_t s);
 
 }  // namespace dash

@@ -797,7 +797,8 @@ class Engine:
         schedule (seed 0) or the seeded round schedule `seed`. Returns dict(trace [num_procs, max_instr]
         u16, lens [num_procs], steps: one SHRINK_STEP_DTYPE record per round (the winner and the base's
         candidate count), report dict). Afterwards every system holds the minimal set, run and checked.
-        cap=k keeps the first k steps (report["rounds"] has their number)."""
+        cap=k keeps the first k steps (report["rounds"] has their number). The library runs it as the
+        one-job case of shrink_many's engine; a source that does not meet the goal is an error here."""
         goal = ShrinkGoal(coh_all, err_all, err_none, 0)
         stride = max(int(self.cfg.max_instr), 1)
         trace = np.zeros((self.num_procs, stride), dtype=np.uint16)
@@ -813,7 +814,7 @@ class Engine:
 
     def shrink_many(self, jobs, cap=None) -> dict:
         """dash_shrink_many: the jobs, rows of (src, seed, coh_all, err_all, err_none), shrunk side by side
-        on the GPU, each to where Engine.shrink would take it alone. Returns dict(trace [J, num_procs,
+        on the GPU, each to where Engine.shrink (the same engine with one job) takes it alone. Returns dict(trace [J, num_procs,
         max_instr] u16, lens [J, num_procs], steps: a list of SHRINK_STEP_DTYPE arrays, results: a
         SHRINK_RESULT_DTYPE array (status SHRINK_MINIMAL or SHRINK_UNMET per job), report dict).
         Afterwards system k holds the final set of job k % J, run and checked. cap=k keeps the first k
