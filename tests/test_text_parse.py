@@ -7,6 +7,7 @@ letting the comparison go quiet."""
 import numpy as np
 import pytest
 
+import sscanf_ref
 import text_corpus as tc
 from oracle_ctypes import GOLDEN
 
@@ -61,7 +62,18 @@ def test_text_equals_file_parser(dash, on_disk, num_procs, max_instr):
 def test_rules_spelled_out(dash):
     P = lambda s, n=4, m=32: (lambda w, rc: (w.tolist(), rc))(*dash.parse_core_text(s, n, m))
     assert P(b"RD 0x\n") == ([0x0000], dash.OK)                   # "0x" without a digit: the 0 is the number
-    assert P(b"WR 0x 5\n") == ([], dash.EPARSE)
+    # where a hand-written scanner and the library's sscanf once parted: a sign on
+    # the hex number, any isspace byte as a blank, a 0x consumed without a digit, saturation at 17
+    # significant hex digits. What each reads is the library's own answer (sscanf_ref.py).
+    S = lambda s, n=4, m=32: (lambda w, rc: (w.tolist(), rc))(*sscanf_ref.parse_core_text(s, n, m))
+    for rec in (b"RD -1\n", b"RD +1f\n", b"RD -0x10\n", b"RD -0xee\n", b"WR -0xff +3\n",
+                b"WR 0x12\r5\n", b"WR\f0x12 5\n", b"WR 0x12\v7\n", b"RD\r0x21\n",
+                b"WR 0x 5\n", b"WR 0X-5\n", b"WR 0xg 5\n", b"RD 0x\0junk\n",
+                b"RD12345678901234567", b"RDffffffffffffffff1", b"RD00000000000000012", b"RD-ffffffffffffffef"):
+        for n in (4, 8):
+            assert P(rec, n) == S(rec, n), (rec, n)
+    assert S(b"RD -0xee\n")[1] == S(b"WR 0x 5\n")[1] == S(b"WR 0x12\r5\n")[1] == dash.OK
+    assert S(b"RDffffffffffffffff1")[1] == dash.EADDR and S(b"WR 0xg 5\n")[1] == dash.EPARSE
     assert P(b"WR 0x15 300\nRD 17\n") == ([0x8000 | 0x1500 | 44, 0x1700], dash.OK)
     assert P(b"WR 0x15 -1") == ([0x8000 | 0x1500 | 255], dash.OK)  # no final newline
     assert P(b"\n") == ([], dash.EPARSE)

@@ -42,26 +42,49 @@ static int hexval(int c) {
     return -1;
 }
 
-/* sscanf "%hhx": optional whitespace, optional 0x prefix, hex digits, value mod 256 */
+/* isspace in the C locale: what a blank in a scanf format and a conversion's leading skip take */
+static int is_blank(int c) { return c == ' ' || (c >= '\t' && c <= '\r'); }
+
+/* sscanf "%hhx" as the C library reads it (tests/sscanf_ref.py holds it to that): blanks, an
+   optional sign, then "0" with an optional x/X (consumed even when no hex digit follows: the 0
+   is then the number), then hex digits; at least one digit in all. The number is an unsigned
+   long that saturates (strtoul) before the cast to a byte: past ULONG_MAX it reads 0xFF, sign
+   or not; otherwise a '-' negates it. */
 static const char *scan_hhx(const char *p, unsigned *out) {
-    while (*p == ' ' || *p == '\t') p++;
-    if (p[0] == '0' && (p[1] == 'x' || p[1] == 'X') && hexval((unsigned char)p[2]) >= 0) p += 2;
-    if (hexval((unsigned char)*p) < 0) return NULL;
-    unsigned v = 0;
-    while (hexval((unsigned char)*p) >= 0) v = (v << 4) | (unsigned)hexval((unsigned char)*p++);
-    *out = v & 0xFFu;
+    while (is_blank((unsigned char)*p)) p++;
+    int neg = 0, any = 0, over = 0;
+    if (*p == '+' || *p == '-') neg = *p++ == '-';
+    if (*p == '0') {
+        any = 1;
+        p++;
+        if (*p == 'x' || *p == 'X') p++;
+    }
+    unsigned long v = 0;
+    for (int d; (d = hexval((unsigned char)*p)) >= 0; p++) {
+        over |= (v >> (sizeof v * 8 - 4)) != 0;
+        v = (v << 4) | (unsigned long)d;
+        any = 1;
+    }
+    if (!any) return NULL;
+    *out = over ? 0xFFu : (unsigned)((neg ? 0ul - v : v) & 0xFFu);
     return p;
 }
 
-/* sscanf "%hhu": optional whitespace, optional sign, decimal digits, value mod 256 */
+/* sscanf "%hhu": blanks, an optional sign, decimal digits (at least one; "0x5" reads 0 and
+   stops at the x), saturating like %hhx -- out of reach inside a 19-byte record, where a WR
+   leaves room for 15 digits. */
 static const char *scan_hhu(const char *p, unsigned *out) {
-    while (*p == ' ' || *p == '\t') p++;
-    int neg = 0;
+    while (is_blank((unsigned char)*p)) p++;
+    int neg = 0, over = 0;
     if (*p == '+' || *p == '-') neg = *p++ == '-';
     if (*p < '0' || *p > '9') return NULL;
-    unsigned v = 0;
-    while (*p >= '0' && *p <= '9') v = v * 10u + (unsigned)(*p++ - '0');
-    *out = (neg ? (0u - v) : v) & 0xFFu;
+    unsigned long v = 0;
+    for (; *p >= '0' && *p <= '9'; p++) {
+        const unsigned long d = (unsigned long)(*p - '0');
+        over |= v > (~0ul - d) / 10ul;
+        v = v * 10ul + d;
+    }
+    *out = over ? 0xFFu : (unsigned)((neg ? 0ul - v : v) & 0xFFu);
     return p;
 }
 

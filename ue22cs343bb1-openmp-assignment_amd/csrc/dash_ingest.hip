@@ -2,7 +2,11 @@
 // simulator's lane-contiguous trace layout. The rules are those of dash_parse_core_text
 // (dash_text.c, its header comment): records of up to 19 bytes ending after '\n', long lines
 // split at 19-byte steps from the line's start, RD %hhx / WR %hhx %hhu, first failing record
-// ends the file, nothing past max_instr accepted records is looked at.
+// ends the file, nothing past max_instr accepted records is looked at. The two conversions
+// follow the C library's sscanf (any isspace byte is a blank, a sign before either number, a
+// "0x" consumed without a digit, saturation at 17 significant hex digits), and no scan leaves
+// its record: it stops at the record's '\n' even where the next record's text would continue
+// the number. tests/test_gpu_text_sscanf.py holds parse_record to the library itself.
 //
 // One 256-thread workgroup per file walks it in tiles of DASH_TEXT_TILE bytes, 16 bytes per
 // lane. Per tile:
@@ -61,8 +65,13 @@ __device__ inline int hexv(uint32_t c) {
     return -1;
 }
 
-// One record: bytes t[s .. lim) of the staged tile; past lim every byte reads as NUL, which,
-// like '\n', no scan steps over. Returns 0 and the packed word, or an INGEST_CODE_*.
+// One record: bytes t[s .. lim) of the staged tile, where lim is the record's furthest possible
+// end (19 bytes on, or the file's end), not its own: a record that ends sooner ends at its '\n',
+// and the next record's bytes follow it below lim. So no scan may step over a '\n': it is no
+// digit and no sign, and `blank` leaves it out (to the library it is a blank, but one that
+// only the end of the line buffer can follow, where the conversion fails all the same). Past
+// lim every byte reads as NUL, which no scan steps over either. Returns 0 and the packed word,
+// or an INGEST_CODE_*.
 __device__ inline uint32_t parse_record(const uint8_t* t, uint32_t s, uint32_t lim, uint32_t num_procs,
                                         uint32_t& word) {
     auto get = [&](uint32_t i) -> uint32_t { return i < lim ? t[i] : 0u; };
@@ -71,21 +80,33 @@ __device__ inline uint32_t parse_record(const uint8_t* t, uint32_t s, uint32_t l
     if (c0 == 'R' && c1 == 'D') wr = false;
     else if (c0 == 'W' && c1 == 'R') wr = true;
     else return INGEST_CODE_PARSE;
+    // isspace in the C locale without '\n': ' ' '\t' '\v' '\f' '\r'
+    auto blank = [](uint32_t c) { return c == ' ' || c == '\t' || c - '\v' < 3u; };
     uint32_t p = s + 2, c;
-    // %hhx
-    while ((c = get(p)) == ' ' || c == '\t') p++;
-    if (c == '0' && (get(p + 1) | 0x20u) == 'x' && hexv(get(p + 2)) >= 0) p += 2;
-    int d = hexv(get(p));
-    if (d < 0) return INGEST_CODE_PARSE;
-    uint32_t addr = 0;
-    do {
+    // %hhx: blanks, a sign, "0" with an x/X that is consumed with or without a digit after it
+    // (the 0 is then the number), hex digits. The library's number is a 64-bit one that
+    // saturates: more than 16 significant digits read 0xFF; otherwise the low byte of the
+    // signed value, for which 32 bits of it are enough.
+    while (blank(c = get(p))) p++;
+    const bool aneg = c == '-';
+    if (c == '+' || c == '-') c = get(++p);
+    bool any = false;
+    if (c == '0') {
+        any = true;
+        c = get(++p);
+        if ((c | 0x20u) == 'x') c = get(++p);
+    }
+    uint32_t addr = 0, sig = 0;
+    for (int d; (d = hexv(c)) >= 0; c = get(++p)) {
         addr = (addr << 4) | (uint32_t)d;
-        d = hexv(get(++p));
-    } while (d >= 0);
-    addr &= 0xFFu;
+        sig += (sig | (uint32_t)d) != 0u;
+        any = true;
+    }
+    if (!any) return INGEST_CODE_PARSE;
+    addr = sig > 16u ? 0xFFu : (aneg ? 0u - addr : addr) & 0xFFu;
     uint32_t val = 0;
-    if (wr) {  // %hhu
-        while ((c = get(p)) == ' ' || c == '\t') p++;
+    if (wr) {  // %hhu: blanks, a sign, decimal digits; 15 at most fit, far from saturation
+        while (blank(c = get(p))) p++;
         const bool neg = c == '-';
         if (c == '+' || c == '-') c = get(++p);
         if (c - '0' >= 10u) return INGEST_CODE_PARSE;

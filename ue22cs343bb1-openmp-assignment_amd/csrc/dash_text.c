@@ -5,7 +5,9 @@
  * one slab. dash_parse_core_text is the in-memory oracle of the device parser
  * (dash_ingest.hip): both restate the rules below.
  *
- * The rules, as they follow from fgets(line, 20) + the sscanf restatements:
+ * The rules are those of fgets(line, 20) + sscanf(line, "RD %hhx") / sscanf(line, "WR %hhx %hhu")
+ * in the C library, as tested: tests/sscanf_ref.py calls the library's sscanf, and
+ * tests/test_text_sscanf.py / test_gpu_text_sscanf.py hold the three parsers to it.
  *   Records   A record is up to 19 bytes and ends after a '\n'. A longer line continues as
  *             further records at 19-byte steps from the line's start. Trailing bytes without
  *             a final newline form a record; zero remaining bytes form none.
@@ -15,11 +17,19 @@
  *             first 19 * max_instr bytes of a file can matter.
  *   RD        "RD" followed by %hhx: a read, value 0 (ref :839).
  *   WR        "WR" followed by %hhx then %hhu: a write.
- *   Else      Any other record, an empty line included, is DASH_EPARSE at that record.
- *   %hhx      Skip ' ' and '\t' only. A 0x/0X prefix counts only when a hex digit follows
- *             it. At least one hex digit. The value is taken mod 256.
- *   %hhu      Skip ' ' and '\t'. An optional '+' or '-'. At least one decimal digit. The
- *             value is taken mod 256; negation is mod 256.
+ *   Else      Any other record, an empty line included, is DASH_EPARSE at that record: so is
+ *             every record in which sscanf would assign fewer fields than its format has.
+ *   Blank     ' ' '\t' '\n' '\v' '\f' '\r' (isspace in the C locale). Any run of blanks, an
+ *             empty one too, may stand before each number; none is needed ("RD12", "WR1-5").
+ *   %hhx      Blanks. An optional '+' or '-'. Then "0" with an optional x/X, which is consumed
+ *             even when no hex digit follows ("WR 0x 5" is address 0, value 5; "WR 0x-5" is
+ *             address 0, value 251); then hex digits. At least one digit in all, the prefix's 0
+ *             included. The number is an unsigned long: one that does not fit (17 significant
+ *             hex digits where long has 64 bits) reads 0xFF, signed or not; otherwise '-'
+ *             negates it, and the low byte is taken ("RD -0x10" is address 0xF0).
+ *   %hhu      Blanks. An optional '+' or '-'. At least one decimal digit ("0x5" reads 0 and
+ *             stops at the x; "- 5" and a lone sign fail). Saturation and negation as for %hhx;
+ *             a record has no room for a decimal number that saturates.
  *   Trailing  Bytes after the numbers are ignored.
  *   Address   Checked after a successful parse: addr >> 4 >= num_procs is DASH_EADDR. A WR
  *             whose value fails to parse is DASH_EPARSE even with a bad address.
@@ -43,25 +53,50 @@ static int hexval(int c) {
     return -1;
 }
 
-/* as in dash_host.c: every scan stops at the record's terminating NUL */
+/* as in dash_host.c; every scan stops at the record's terminating NUL.
+   isspace in the C locale: what a blank in a scanf format and a conversion's leading skip take */
+static int is_blank(int c) { return c == ' ' || (c >= '\t' && c <= '\r'); }
+
+/* sscanf "%hhx" as the C library reads it (tests/sscanf_ref.py holds it to that): blanks, an
+   optional sign, then "0" with an optional x/X (consumed even when no hex digit follows: the 0
+   is then the number), then hex digits; at least one digit in all. The number is an unsigned
+   long that saturates (strtoul) before the cast to a byte: past ULONG_MAX it reads 0xFF, sign
+   or not; otherwise a '-' negates it. */
 static const char *scan_hhx(const char *p, unsigned *out) {
-    while (*p == ' ' || *p == '\t') p++;
-    if (p[0] == '0' && (p[1] == 'x' || p[1] == 'X') && hexval((unsigned char)p[2]) >= 0) p += 2;
-    if (hexval((unsigned char)*p) < 0) return NULL;
-    unsigned v = 0;
-    while (hexval((unsigned char)*p) >= 0) v = (v << 4) | (unsigned)hexval((unsigned char)*p++);
-    *out = v & 0xFFu;
+    while (is_blank((unsigned char)*p)) p++;
+    int neg = 0, any = 0, over = 0;
+    if (*p == '+' || *p == '-') neg = *p++ == '-';
+    if (*p == '0') {
+        any = 1;
+        p++;
+        if (*p == 'x' || *p == 'X') p++;
+    }
+    unsigned long v = 0;
+    for (int d; (d = hexval((unsigned char)*p)) >= 0; p++) {
+        over |= (v >> (sizeof v * 8 - 4)) != 0;
+        v = (v << 4) | (unsigned long)d;
+        any = 1;
+    }
+    if (!any) return NULL;
+    *out = over ? 0xFFu : (unsigned)((neg ? 0ul - v : v) & 0xFFu);
     return p;
 }
 
+/* sscanf "%hhu": blanks, an optional sign, decimal digits (at least one; "0x5" reads 0 and
+   stops at the x), saturating like %hhx -- out of reach inside a 19-byte record, where a WR
+   leaves room for 15 digits. */
 static const char *scan_hhu(const char *p, unsigned *out) {
-    while (*p == ' ' || *p == '\t') p++;
-    int neg = 0;
+    while (is_blank((unsigned char)*p)) p++;
+    int neg = 0, over = 0;
     if (*p == '+' || *p == '-') neg = *p++ == '-';
     if (*p < '0' || *p > '9') return NULL;
-    unsigned v = 0;
-    while (*p >= '0' && *p <= '9') v = v * 10u + (unsigned)(*p++ - '0');
-    *out = (neg ? (0u - v) : v) & 0xFFu;
+    unsigned long v = 0;
+    for (; *p >= '0' && *p <= '9'; p++) {
+        const unsigned long d = (unsigned long)(*p - '0');
+        over |= v > (~0ul - d) / 10ul;
+        v = v * 10ul + d;
+    }
+    *out = over ? 0xFFu : (unsigned)((neg ? 0ul - v : v) & 0xFFu);
     return p;
 }
 
