@@ -74,6 +74,10 @@ static_assert(DASH_WCHUNK_CS8 == 2 || DASH_WCHUNK_CS8 == 4, "window chunk");
 #ifndef DASH_HOT_LAYOUT
 #define DASH_HOT_LAYOUT 1          // 1: the cold blocks of the round and of the trip start lie behind the loop
 #endif
+// Ring stores of the same kernels' non-final tiers (A/B builds):
+#ifndef DASH_FLAT_PLACE
+#define DASH_FLAT_PLACE 1          // 1: both receivers' slots are read and ranked in every lane, the masked regions hold the store alone
+#endif
 
 // message word (ref `message`, :70-79, 20 B -> 4 B):
 //   [3:0] type  [6:4] sender  [7] dirState == S (REPLY_RD)  [14:8] address
@@ -262,6 +266,11 @@ void sim_kernel(const SimArgs a) {
     // The same kernels keep the round loop's common path free of taken branches: every rare block
     // (OOB accounting, REPLY_ID fan-out, round cap, overflow stop) is placed behind the loop
     constexpr bool HOT = DASH_HOT_LAYOUT && MODE == 0 && CS == 4;
+    // Below the final tier the same kernels read and rank the slots of both ring stores of a round in
+    // every lane, so each store's exec-masked region holds one LDS write and the compiler emits it
+    // without a skip branch (the delivery tail of step(); the final tier keeps place(): its
+    // capacity test and cold block)
+    constexpr bool FLAT = DASH_FLAT_PLACE && MODE == 0 && CS == 4 && RING != 256;
     using L = Lds<P, CS, RING>;
     constexpr uint32_t WCHUNK = wchunk_of<CS>();
     using wchunk_t = typename std::conditional<WCHUNK == 4, uint2, uint32_t>::type;
@@ -854,8 +863,41 @@ void sim_kernel(const SimArgs a) {
                 }
             }
         }
-        place(xVP, xdP, bitP, xwP);
-        place(xVB, msr, bitB, wA);
+        if constexpr (FLAT) {
+            // Both receivers' (mask, tail) pairs are read and both slots ranked before either store,
+            // in every lane, and the offsets and words are pinned in VGPRs: a masked region that held
+            // the read, its wait and the rank arithmetic too (the store was their only user, so the
+            // compiler sank them into it) was emitted behind an s_cbranch_execz; one that holds the
+            // LDS write alone is s_and_saveexec / ds_write / s_or exec, like the arrival ORs above.
+            // Every arrival OR of the round, the fan-out's included, is above, so the ranks see all
+            // arrivals; the stores touch RNG alone, neither the masks nor the tails, so reading the
+            // second receiver before the first store changes nothing its rank sees. The two reads
+            // issue back to back.
+            // Lanes that send nothing read too, so the index must be in range in every lane:
+            //   msr = m >> 28 <= 15 whatever the ring word holds;
+            //   xdP = dP is dE = laddr >> 4 <= 15 (laddr is a byte; 15: a never-filled line) where
+            //   the lane has no reply to send, else dA: msender or H (<= 7), es_own under mEsOne (one
+            //   bit in es_bv) or own at an EM entry, whose bitVector holds exactly one bit (the
+            //   invariant of NO_CTZ0, which the masked arrival OR above relies on already). A lane
+            //   whose own / es_own is ffbl(0) -- no request at EM, an EVICT_SHARED that leaves no or
+            //   several sharers -- never selects it.
+            // So a lane reads words seg + d and 65 + seg + d with seg <= 63, d <= 15: inside MQ or the
+            // counters behind it, never outside the workgroup's allocation.
+            static_assert(L::MQT + 63 + 15 < L::WORDS, "an idle lane's slot read stays inside the LDS");
+            const uint32_t rP = L::MQS * (seg + xdP), rB = L::MQS * (seg + msr);
+            const uint2 qP = make_uint2(lds[L::MQM + rP], lds[L::MQT + rP]);
+            const uint2 qB = make_uint2(lds[L::MQM + rB], lds[L::MQT + rB]);
+            const uint32_t rankP = (uint32_t)__builtin_popcount(qP.x & (bitP - 1u));
+            const uint32_t rankB = (uint32_t)__builtin_popcount(qB.x & (bitB - 1u));
+            uint32_t offP = (qP.y + (rankP << 8)) & RMASK, offB = (qB.y + (rankB << 8)) & RMASK;
+            uint32_t swP = xwP, swB = wA;
+            asm volatile("" : "+v"(offP), "+v"(swP), "+v"(offB), "+v"(swB));
+            if (B(xVP)) *reinterpret_cast<uint32_t*>(ldsb + L::RNG * 4 + offP) = swP;
+            if (B(xVB)) *reinterpret_cast<uint32_t*>(ldsb + L::RNG * 4 + offB) = swB;
+        } else {
+            place(xVP, xdP, bitP, xwP);
+            place(xVB, msr, bitB, wA);
+        }
         const uint32_t arrived = __hip_atomic_exchange(&lds[L::MQM + L::MQS * lane], 0u, __ATOMIC_RELAXED,
                                                        __HIP_MEMORY_SCOPE_WORKGROUP);
         uint32_t n = (uint32_t)__builtin_popcount(arrived) << 8;
