@@ -388,6 +388,81 @@ int dash_compute_metrics(dash_t *h, dash_metrics_totals *totals);
 int dash_read_metrics(dash_t *h, uint64_t first, uint64_t count, dash_node_metrics *out,
                       uint8_t *truncated);
 
+/* ---- per-address sharing profile, reduced on the device from the event log
+   (csrc/dash_addr.hip) ----
+   The second axis of the per-node metrics: the same log, by address. An address is
+   a = (home << 4) | block, a < A = num_procs * 16; an event's address is bits 14:8 of its word, for
+   instructions and popped messages alike. The events are those of the kept rounds [0, K),
+   K = min(rounds[sys], the log's rounds), exactly as above; the delivery markers of seeded micro-step
+   schedules are not events. Every field of address a's record is a sum or an OR over the events whose
+   address is a, so nothing depends on their order:
+
+   reads, writes          instruction events, by bit 15 of the instruction (set = WR)
+   read_misses, write_misses, upgrades
+                          READ_REQUEST / WRITE_REQUEST / UPGRADE message events, whoever pops them
+   invalidations          INV popped, at any node
+   interventions          WRITEBACK_INV + WRITEBACK_INT popped
+   flushes                FLUSH + FLUSH_INVACK popped: the cache-to-cache supplies
+   evict_shared, evict_modified
+                          EVICT_SHARED / EVICT_MODIFIED popped at the home only (node == a >> 4), as in
+                          dash_node_metrics: the home's forwarded EVICT_SHARED is popped elsewhere
+   msgs                   every message event
+   nodes                  readers | writers << 8 | invalidated << 16: bit t of each byte is set when
+                          node t issued an RD / issued a WR / popped an INV on a
+
+   An event whose address is >= A belongs to no record; the totals count it in foreign_events, so the
+   records and that count together hold every event. Every load refuses a trace address homed on a
+   node >= num_procs (DASH_EADDR), so no run of loaded traces has one. A field wraps at 2^32, which
+   takes more than 2^29 kept rounds of one system. */
+typedef struct dash_addr_metrics {
+    uint32_t reads, writes;
+    uint32_t read_misses, write_misses, upgrades;
+    uint32_t invalidations, interventions, flushes;
+    uint32_t evict_shared, evict_modified;
+    uint32_t msgs;
+    uint32_t nodes;
+} dash_addr_metrics; /* 12 x uint32_t: 48 B per address */
+/* The class of a record, with r = nodes & 0xFF and w = (nodes >> 8) & 0xFF; "two or more nodes" is
+   popcount(r | w) >= 2. A touched record has a bit in r | w, so exactly one class holds: */
+#define DASH_ADDR_UNTOUCHED 0    /* reads + writes == 0 */
+#define DASH_ADDR_PRIVATE 1      /* popcount(r | w) == 1 */
+#define DASH_ADDR_READ_SHARED 2  /* w == 0, two or more nodes */
+#define DASH_ADDR_ONE_WRITER 3   /* popcount(w) == 1, two or more nodes */
+#define DASH_ADDR_MULTI_WRITER 4 /* popcount(w) >= 2 */
+/* Pure host code, the arithmetic the device uses (addr_class in csrc/dash_addr.h); DASH_EINVAL for NULL.
+   (A hand-made record with reads + writes != 0 and r | w == 0 comes back as DASH_ADDR_PRIVATE.) */
+int dash_addr_class(const dash_addr_metrics *m);
+/* Over every record of the batch: the sums of the first eleven fields, the largest msgs of any record,
+   the events that fell in no record, and per class (DASH_ADDR_*) the records, their read_misses +
+   write_misses + upgrades and their invalidations; the systems, and those whose log was shorter than
+   their run. */
+typedef struct dash_addr_totals {
+    uint64_t reads, writes;
+    uint64_t read_misses, write_misses, upgrades;
+    uint64_t invalidations, interventions, flushes;
+    uint64_t evict_shared, evict_modified;
+    uint64_t msgs;
+    uint64_t msgs_max;
+    uint64_t foreign_events;
+    uint64_t class_addrs[5], class_misses[5], class_invalidations[5];
+    uint64_t systems, truncated_systems;
+} dash_addr_totals;
+/* One pass of the device over the whole batch's event log of the last dash_run (any schedule; after
+   dash_explore*, the last pass): num_procs * 16 dash_addr_metrics records per system stay on the device
+   until the next dash_run, and the totals (optional) are on the host at return. State rules as
+   dash_compute_metrics: DASH_ESTATE before a completed dash_run and on a handle created with
+   trace_events == 0; a log shorter than a system's run is no error (the records cover the log's
+   rounds, the `truncated` byte is set and the system counts in truncated_systems). The record buffer,
+   num_systems x num_procs x 16 x 48 B, is allocated by the first call: DASH_ENOMEM when it does not
+   fit, and the handle stays usable. These records and dash_compute_metrics' are valid independently
+   of each other. */
+int dash_compute_addr_metrics(dash_t *h, dash_addr_totals *totals);
+/* Records of systems [first, first + count): out[(k - first) * num_procs * 16 + a], and (optional)
+   truncated[k - first]. DASH_ESTATE when no dash_compute_addr_metrics followed the last dash_run;
+   DASH_EINVAL for a range outside the batch. */
+int dash_read_addr_metrics(dash_t *h, uint64_t first, uint64_t count, dash_addr_metrics *out,
+                           uint8_t *truncated);
+
 /* ---- coherence invariants of final states (csrc/dash_coherence.hip) ----
    An address is a = (home << 4) | block with home < num_procs and block < 16: a system has
    num_procs * 16 addresses. Over the final state of one system, the copies of a are the cache lines
@@ -766,6 +841,13 @@ uint64_t dash_digest_node(const dash_node_state *s, uint32_t node_id, uint32_t c
    1..8 or cache_size 1..16. */
 int dash_check_states(const dash_node_state *nodes, uint32_t num_procs, uint32_t cache_size,
                       dash_coherence *out, uint32_t *addr_bits);
+/* The per-address records (dash_addr_metrics, above) of one system whose events the caller holds, e.g.
+   what dash_read_events returned: the library's one statement of the rules on the host. Events of
+   rounds >= `rounds` are ignored, so `rounds` is the K of the rules; out gets all num_procs * 16
+   records, *foreign (optional) the events whose address is num_procs * 16 or more. DASH_EINVAL for
+   num_procs outside 1..8, a NULL out, or a NULL ev with n != 0. */
+int dash_addr_metrics_from_events(const dash_event *ev, uint64_t n, uint32_t num_procs, uint32_t rounds,
+                                  dash_addr_metrics *out /* [num_procs * 16] */, uint64_t *foreign /* or NULL */);
 /* One event as the reference prints it: DEBUG_MSG "Processor %d msg from: %d, type: %d,
    address: 0x%02X" (ref :180-181) or DEBUG_INSTR "Processor %d: instr type=%c,
    address=0x%02X, value=%hhu" (ref :650-651), newline included. Returns bytes or < 0. */

@@ -33,6 +33,13 @@
  *       evict_modified= home_requests= waits= wait_mean= wait_max= idle_rounds=" (wait_mean and
  *       wait_max in rounds; include/dash.h defines each count). Goes with --schedule, --rounds,
  *       --micro and --micro-seed; in the bulk modes it prints one "metrics total ..." line
+ *   --addr-metrics    the per-address sharing profile, reduced on the GPU from the same log
+ *       (dash_compute_addr_metrics); accepted wherever --metrics is, and together with it. After the dumps
+ *       (and the --metrics lines), one stdout line per address whose class is not untouched, in ascending
+ *       address order: "addr 0x<AA> class=<private|read_shared|one_writer|multi_writer> reads= writes=
+ *       read_misses= write_misses= upgrades= invalidations= interventions= flushes= evict_shared=
+ *       evict_modified= msgs= readers=0x<BB> writers=0x<BB> invalidated=0x<BB>" (include/dash.h defines
+ *       each); in the bulk modes one "addr total ..." line with the totals and the five class counts
  *   --coherence       the coherence invariants of the final state, checked on the GPU
  *       (dash_check_coherence; include/dash.h defines the DASH_COH_* bits): after the dumps, one stdout
  *       line "coherence addrs=<K> bits=0x<BB>", K = addresses that break an invariant, followed by
@@ -271,6 +278,40 @@ static int print_metrics(dash_t *h, uint64_t count, unsigned n) {
     return rc;
 }
 
+/* --addr-metrics: the one system's touched addresses, one line each (count 1), or the totals */
+static int print_addr_metrics(dash_t *h, uint64_t count, unsigned n) {
+    static const char *classes[5] = {"untouched", "private", "read_shared", "one_writer", "multi_writer"};
+    dash_addr_totals tot;
+    int rc = dash_compute_addr_metrics(h, &tot);
+    if (rc != DASH_OK) return rc;
+    if (count != 1) {
+        printf("addr total systems=%llu truncated_systems=%llu", (unsigned long long)tot.systems,
+               (unsigned long long)tot.truncated_systems);
+        static const char *names[13] = {"reads", "writes", "read_misses", "write_misses", "upgrades", "invalidations",
+                                        "interventions", "flushes", "evict_shared", "evict_modified", "msgs",
+                                        "msgs_max", "foreign_events"};
+        uint64_t v[13]; /* these 13 fields lead the struct */
+        memcpy(v, &tot, sizeof v);
+        for (int k = 0; k < 13; k++) printf(" %s=%llu", names[k], (unsigned long long)v[k]);
+        for (int k = 0; k < 5; k++) printf(" %s=%llu", classes[k], (unsigned long long)tot.class_addrs[k]);
+        printf("\n");
+        return DASH_OK;
+    }
+    dash_addr_metrics m[DASH_MAX_PROCS * DASH_MEM_SIZE];
+    rc = dash_read_addr_metrics(h, 0, 1, m, NULL);
+    for (unsigned a = 0; rc == DASH_OK && a < n * DASH_MEM_SIZE; a++) {
+        const int c = dash_addr_class(&m[a]);
+        if (c == DASH_ADDR_UNTOUCHED) continue;
+        printf("addr 0x%02X class=%s reads=%u writes=%u read_misses=%u write_misses=%u upgrades=%u invalidations=%u "
+               "interventions=%u flushes=%u evict_shared=%u evict_modified=%u msgs=%u readers=0x%02X writers=0x%02X "
+               "invalidated=0x%02X\n",
+               a, classes[c], m[a].reads, m[a].writes, m[a].read_misses, m[a].write_misses, m[a].upgrades,
+               m[a].invalidations, m[a].interventions, m[a].flushes, m[a].evict_shared, m[a].evict_modified, m[a].msgs,
+               m[a].nodes & 0xFFu, (m[a].nodes >> 8) & 0xFFu, (m[a].nodes >> 16) & 0xFFu);
+    }
+    return rc;
+}
+
 /* --coherence: the one system's record as a line */
 static int print_coherence(dash_t *h) {
     dash_coherence c;
@@ -288,7 +329,8 @@ static int print_coherence(dash_t *h) {
 static int simulate_traced(const char *dir, unsigned n, unsigned cs, unsigned m, const char *out, int dev,
                            int dbg_instr, int dbg_msg, unsigned long long sched, const uint8_t *rounds,
                            long nrounds, int micro, const uint64_t *mseed, uint64_t weights,
-                           const char *write_micro_file, int metrics, int coherence, dash_stats *st) {
+                           const char *write_micro_file, int metrics, int addr_metrics, int coherence,
+                           dash_stats *st) {
     dash_cfg cfg = {0};
     cfg.num_procs = n;
     cfg.cache_size = cs;
@@ -300,7 +342,7 @@ static int simulate_traced(const char *dir, unsigned n, unsigned cs, unsigned m,
        up to 2^22): n x 4 B per round on the device */
     uint64_t log_rounds = 1024u + 256ull * m;
     if (log_rounds > (1u << 22)) log_rounds = 1u << 22;
-    cfg.trace_events = (dbg_instr || dbg_msg || write_micro_file || metrics) ? (uint32_t)log_rounds : 0;
+    cfg.trace_events = (dbg_instr || dbg_msg || write_micro_file || metrics || addr_metrics) ? (uint32_t)log_rounds : 0;
     cfg.schedule_seed = (rounds || mseed) ? (sched ? sched : 1) : sched;
     dash_t *h = NULL;
     int rc = dash_create(&cfg, &h);
@@ -336,6 +378,7 @@ static int simulate_traced(const char *dir, unsigned n, unsigned cs, unsigned m,
         }
         free(ev);
         if (rc == DASH_OK && metrics) rc = print_metrics(h, 1, n);
+        if (rc == DASH_OK && addr_metrics) rc = print_addr_metrics(h, 1, n);
         if (rc == DASH_OK && coherence) rc = print_coherence(h);
     }
     if (rc != DASH_OK) fprintf(stderr, "%s\n", dash_last_error(h));
@@ -799,7 +842,7 @@ typedef struct {
     unsigned long long seed, sched;
     int dev, show;
     const char *out, *digests, *dump;
-    int device_ingest, metrics;
+    int device_ingest, metrics, addr_metrics;
 } bulk_opts;
 
 static void print_stats(const dash_stats *st);
@@ -866,13 +909,15 @@ static int run_batch_list(const char *list, const bulk_opts *o) {
     else if (h)
         fprintf(stderr, "%s\n", dash_last_error(h));
     dash_destroy(h);
-    if (rc == DASH_OK && o->metrics) {  /* once more, with an event log of the rounds the run took */
+    if (rc == DASH_OK && (o->metrics || o->addr_metrics)) {  /* once more, with an event log of the rounds the run took */
         cfg.flags = 0;
         cfg.trace_events = log_rounds_of(&st);
         h = NULL;
         if ((rc = dash_create(&cfg, &h)) == DASH_OK && (rc = dash_load_dirs(h, (const char *const *)dirs, n)) == DASH_OK &&
-            (rc = dash_run(h, NULL)) == DASH_OK)
-            rc = print_metrics(h, 0, o->n);
+            (rc = dash_run(h, NULL)) == DASH_OK) {
+            if (o->metrics) rc = print_metrics(h, 0, o->n);
+            if (rc == DASH_OK && o->addr_metrics) rc = print_addr_metrics(h, 0, o->n);
+        }
         if (rc != DASH_OK) fprintf(stderr, "%s\n", h ? dash_last_error(h) : dash_last_error(NULL));
         dash_destroy(h);
     }
@@ -906,13 +951,15 @@ static int run_synthetic(uint64_t count, const bulk_opts *o) {
         fprintf(stderr, "%s\n", dash_last_error(h));
     }
     dash_destroy(h);
-    if (rc == DASH_OK && o->metrics) {  /* once more, with an event log of the rounds the run took */
+    if (rc == DASH_OK && (o->metrics || o->addr_metrics)) {  /* once more, with an event log of the rounds the run took */
         cfg.flags = 0;
         cfg.trace_events = log_rounds_of(&st);
         h = NULL;
         if ((rc = dash_create(&cfg, &h)) == DASH_OK && (rc = dash_generate(h, &g)) == DASH_OK &&
-            (rc = dash_run(h, NULL)) == DASH_OK)
-            rc = print_metrics(h, 0, o->n);
+            (rc = dash_run(h, NULL)) == DASH_OK) {
+            if (o->metrics) rc = print_metrics(h, 0, o->n);
+            if (rc == DASH_OK && o->addr_metrics) rc = print_addr_metrics(h, 0, o->n);
+        }
         if (rc != DASH_OK) fprintf(stderr, "%s\n", h ? dash_last_error(h) : dash_last_error(NULL));
         dash_destroy(h);
     }
@@ -927,7 +974,7 @@ int main(int argc, char *argv[]) {
                *sources_file = NULL, *shrink_out = NULL;
     uint32_t shrink_bits = 0;
     unsigned long long synth = 0, seed = 0x5EED, sched = 0, explore = 0, micro_seed = 0;
-    int explore_given = 0, explore_micro = 0, micro_seed_given = 0, metrics = 0, coherence = 0;
+    int explore_given = 0, explore_micro = 0, micro_seed_given = 0, metrics = 0, addr_metrics = 0, coherence = 0;
     uint64_t weights = DASH_MICRO_UNIFORM;
     unsigned len = 4096, kind = DASH_GEN_UNIFORM;
     double loc = 0.5;
@@ -941,6 +988,7 @@ int main(int argc, char *argv[]) {
         else if (!strcmp(argv[i], "--debug-instr")) dbg_instr = 1;
         else if (!strcmp(argv[i], "--debug-msg")) dbg_msg = 1;
         else if (!strcmp(argv[i], "--metrics")) metrics = 1;
+        else if (!strcmp(argv[i], "--addr-metrics")) addr_metrics = 1;
         else if (!strcmp(argv[i], "--coherence")) coherence = 1;
         else if (!strcmp(argv[i], "--batch") && i + 1 < argc) batch = argv[++i];
         else if (!strcmp(argv[i], "--device-ingest")) device_ingest = 1;
@@ -973,7 +1021,7 @@ int main(int argc, char *argv[]) {
     if (batch || synth) {
         if (synth && !n_given) n = 8; /* synthetic systems default to 8 nodes (BASELINE configs) */
         bulk_opts o = {n, cs, m, len, kind, (unsigned)(loc * 65536.0), seed, sched, dev, show, out, digests, dump,
-                       device_ingest, metrics};
+                       device_ingest, metrics, addr_metrics};
         if (o.locality > 65536u) o.locality = 65536u;
         int rc = batch ? run_batch_list(batch, &o) : run_synthetic(synth, &o);
         return rc == DASH_OK ? EXIT_SUCCESS : EXIT_FAILURE;
@@ -981,6 +1029,7 @@ int main(int argc, char *argv[]) {
     if (!dir) {
         fprintf(stderr, "Usage: %s <test_directory>\n", argv[0]); /* ref :128 */
         fprintf(stderr, "       %s <test_directory> --metrics   per-node miss, invalidation and wait metrics\n", argv[0]);
+        fprintf(stderr, "       %s <test_directory> --addr-metrics   per-address traffic, sharers and sharing class\n", argv[0]);
         fprintf(stderr, "       %s <test_directory> --coherence   coherence invariants of the final state\n", argv[0]);
         fprintf(stderr, "       %s <test_directory> --shrink OUTDIR   a minimal trace set with the same broken state\n", argv[0]);
         fprintf(stderr, "       %s <test_directory> --shrink OUTDIR --sources LIST   the same for many directories at once\n", argv[0]);
@@ -1006,7 +1055,7 @@ int main(int argc, char *argv[]) {
         /* with --explore K --coherence: one job per incoherent outcome; with --sources: one per directory */
         const int outcomes = explore_given && !explore_micro && coherence && !sources_file && !shrink_bits;
         if ((explore_given && !outcomes) || rounds_file || micro_file || micro_seed_given || write_rounds_file ||
-            write_micro_file || metrics || (coherence && !outcomes)) {
+            write_micro_file || metrics || addr_metrics || (coherence && !outcomes)) {
             fprintf(stderr, "cache_simulator: --shrink goes with --schedule, --shrink-bits and --sources, or with "
                             "--explore K --coherence [--schedule S0]\n");
             return EXIT_FAILURE;
@@ -1021,9 +1070,9 @@ int main(int argc, char *argv[]) {
         return rc == DASH_OK ? EXIT_SUCCESS : EXIT_FAILURE;
     }
     if (explore_given) {
-        if (rounds_file || micro_file || write_rounds_file || write_micro_file || metrics) {
-            fprintf(stderr, "cache_simulator: --explore takes no --rounds, --micro, --write-rounds, --write-micro "
-                            "or --metrics\n");
+        if (rounds_file || micro_file || write_rounds_file || write_micro_file || metrics || addr_metrics) {
+            fprintf(stderr, "cache_simulator: --explore takes no --rounds, --micro, --write-rounds, --write-micro, "
+                            "--metrics or --addr-metrics\n");
             return EXIT_FAILURE;
         }
         const unsigned long long s0 = explore_micro ? micro_seed : sched;
@@ -1068,10 +1117,11 @@ int main(int argc, char *argv[]) {
     }
     dash_stats st;
     const uint64_t mseed = micro_seed;
-    int rc = (dbg_instr || dbg_msg || sched || rounds || write_rounds_file || micro_seed_given || metrics || coherence)
+    int rc = (dbg_instr || dbg_msg || sched || rounds || write_rounds_file || micro_seed_given || metrics || addr_metrics ||
+              coherence)
                  ? simulate_traced(dir, n, cs, m, out, dev, dbg_instr, dbg_msg, sched, rounds, nrounds,
                                    micro_file != NULL, micro_seed_given ? &mseed : NULL, weights, write_micro_file,
-                                   metrics, coherence, &st)
+                                   metrics, addr_metrics, coherence, &st)
                  : dash_simulate_dir(dir, n, cs, m, out, dev, &st);
     free(rounds);
     if (rc == DASH_OK && write_rounds_file &&

@@ -265,6 +265,7 @@ int dash_run(dash_t* h, dash_stats* stats) {
     if (!h->loaded) return fail(h, DASH_ESTATE, "no traces loaded");
     h->met.valid = false;  // dash_compute_metrics' records are the previous run's
     h->coh.valid = false;  // and dash_check_coherence's
+    h->adr.valid = false;  // and dash_compute_addr_metrics'
     dash::SimArgs a = sim_args(h);
     const uint64_t spw = 64 / h->seg;
     HIPCHK(h, hipSetDevice(h->cfg.device));

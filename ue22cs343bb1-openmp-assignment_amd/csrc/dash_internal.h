@@ -1,7 +1,7 @@
 // dash_internal.h -- what the host files of libdash share: the handle, the error plumbing and
 // the helpers for device buffers and threads. Internal: not installed, not part of dash.h.
 // (dash_core.cpp, dash_sched.cpp, dash_load.cpp, dash_tools.cpp, dash_metrics.cpp,
-// dash_coherence.cpp, dash_outcomes.cpp, dash_shrink.cpp)
+// dash_coherence.cpp, dash_outcomes.cpp, dash_shrink.cpp, dash_addr.cpp)
 //
 // Four mechanisms are written here once, and a new search call is written against them:
 //  * What voids results. traces_changed and schedule_changed are the only places that mark the
@@ -72,7 +72,7 @@ struct dash_ctx {
     struct {
         void* p;
         bool pinned;
-    } owned[48] = {};
+    } owned[56] = {};
     hipEvent_t events[18] = {};  // the stage timers' events: timer_ready enters them, release() destroys them
     uint2* d_trace = nullptr;
     uint32_t* d_lens = nullptr;
@@ -115,6 +115,12 @@ struct dash_ctx {
         unsigned long long* d_tot = nullptr;   // [dash::TOT_WORDS]
         bool valid = false;                    // the records are those of the last run
     } met;
+    struct {  // dash_compute_addr_metrics (dash_addr.cpp): likewise
+        uint4* d_rec = nullptr;                // [num_systems * num_procs * 16] 48-B records, 3 uint4 each
+        uint8_t* d_cut = nullptr;              // [num_systems] log shorter than the run
+        unsigned long long* d_tot = nullptr;   // [dash::ADT_WORDS]
+        bool valid = false;                    // the records are those of the last run
+    } adr;
     struct {  // dash_check_coherence (dash_coherence.cpp): likewise
         uint4* d_rec = nullptr;                // [num_systems] dash_coherence records
         unsigned long long* d_tot = nullptr;   // [dash::COH_TOT_WORDS]

@@ -26,6 +26,9 @@ libdash:
     Engine.read_state(sys)         -> the nodes' processorNode state
     Engine.compute_metrics()       -> per-node miss / invalidation / wait metrics, reduced on the GPU
                                       from the event log (read_metrics returns the records)
+    Engine.compute_addr_metrics()  -> the same log by address: traffic, sharers and a sharing class per
+                                      cache line (read_addr_metrics returns the records; addr_class and
+                                      addr_metrics_from_events are the same rules on the host)
     Engine.check_coherence()       -> the coherence invariants of every final state, checked on the GPU
                                       (read_coherence returns the records; check_outcomes classifies
                                       an explore's outcomes; check_states is the same on the host)
@@ -84,7 +87,8 @@ EXPORTS = ("dash_create", "dash_destroy", "dash_last_error", "dash_load_traces",
            "dash_read_metrics", "dash_check_states", "dash_check_coherence", "dash_read_coherence",
            "dash_check_outcomes", "dash_explore_sources", "dash_explore_assign", "dash_shrink",
            "dash_shrink_candidate", "dash_write_dir", "dash_test_write_states", "dash_shrink_many",
-           "dash_shrink_assign")
+           "dash_shrink_assign", "dash_compute_addr_metrics", "dash_read_addr_metrics", "dash_addr_class",
+           "dash_addr_metrics_from_events")
 TEXT_TILE = 4096  # DASH_TEXT_TILE: bytes per tile of the device text parser
 SIT_OUT = 0xFF
 MICRO_STEP, MICRO_SEND = 0, 1  # dash_set_micro_schedule actions
@@ -168,6 +172,25 @@ class NodeMetrics(ctypes.Structure):
 
 class MetricsTotals(ctypes.Structure):
     _fields_ = [(f, ctypes.c_uint64) for f in METRIC_FIELDS + ("systems", "truncated_systems")]
+
+
+# dash_addr_metrics / dash_addr_totals (include/dash.h states what each field counts)
+ADDR_METRIC_FIELDS = ("reads", "writes", "read_misses", "write_misses", "upgrades", "invalidations", "interventions",
+                      "flushes", "evict_shared", "evict_modified", "msgs", "nodes")
+ADDR_METRICS_DTYPE = np.dtype([(f, np.uint32) for f in ADDR_METRIC_FIELDS])
+assert ADDR_METRICS_DTYPE.itemsize == 48
+ADDR_UNTOUCHED, ADDR_PRIVATE, ADDR_READ_SHARED, ADDR_ONE_WRITER, ADDR_MULTI_WRITER = range(5)  # DASH_ADDR_*
+ADDR_CLASS_NAMES = ("untouched", "private", "read_shared", "one_writer", "multi_writer")
+
+
+class AddrMetrics(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint32) for f in ADDR_METRIC_FIELDS]
+
+
+class AddrTotals(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint64) for f in ADDR_METRIC_FIELDS[:11] + ("msgs_max", "foreign_events")] + \
+               [(f, ctypes.c_uint64 * 5) for f in ("class_addrs", "class_misses", "class_invalidations")] + \
+               [(f, ctypes.c_uint64) for f in ("systems", "truncated_systems")]
 
 
 # DASH_COH_*: the invariants an address can break (include/dash.h states each)
@@ -332,6 +355,10 @@ def lib() -> ctypes.CDLL:
         "dash_shrink_many": (i32, [vp, vp, u64, vp, u64, vp, vp, u32, vp, ctypes.POINTER(ShrinkManyReport)]),
         "dash_shrink_assign": (i32, [vp, u64, u64, u64, u64, ctypes.POINTER(u64), ctypes.POINTER(u64),
                                      ctypes.POINTER(i32)]),
+        "dash_compute_addr_metrics": (i32, [vp, ctypes.POINTER(AddrTotals)]),
+        "dash_read_addr_metrics": (i32, [vp, u64, u64, vp, vp]),
+        "dash_addr_class": (i32, [ctypes.POINTER(AddrMetrics)]),
+        "dash_addr_metrics_from_events": (i32, [vp, u64, u32, u32, vp, ctypes.POINTER(u64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -457,6 +484,31 @@ def check_states(nodes, num_procs: int, cache_size: int):
     _check(lib().dash_check_states(arr, num_procs, cache_size, ctypes.byref(rec), bits.ctypes.data),
            "dash_check_states")
     return {f: int(getattr(rec, f)) for f in COHERENCE_FIELDS}, bits[:num_procs * MEM_SIZE].copy()
+
+
+def addr_class(record) -> int:
+    """dash_addr_class: the sharing class (ADDR_UNTOUCHED .. ADDR_MULTI_WRITER) of one per-address record,
+    a mapping or structured-array element with the ADDR_METRIC_FIELDS."""
+    m = AddrMetrics(**{f: int(record[f]) for f in ADDR_METRIC_FIELDS})
+    c = lib().dash_addr_class(ctypes.byref(m))
+    _check(c if c < 0 else OK, "dash_addr_class")
+    return c
+
+
+def addr_metrics_from_events(events, num_procs: int, rounds: int):
+    """dash_addr_metrics_from_events: the per-address records of one system from its events
+    (Engine.read_events' list, or (round, node, kind, word) tuples), over the rounds < `rounds`.
+    Returns (records, a structured array [num_procs * 16] with the ADDR_METRIC_FIELDS; the number of
+    events whose address is num_procs * 16 or more)."""
+    arr = (Event * max(len(events), 1))()
+    for k, e in enumerate(events):
+        arr[k] = e if isinstance(e, Event) else Event(*[int(x) for x in e])
+    rec = np.zeros(max(num_procs, 0) * MEM_SIZE if num_procs <= MAX_PROCS else 0, dtype=ADDR_METRICS_DTYPE)
+    out = rec if rec.size else np.zeros(1, dtype=ADDR_METRICS_DTYPE)
+    foreign = ctypes.c_uint64()
+    _check(lib().dash_addr_metrics_from_events(arr, len(events), num_procs, rounds, out.ctypes.data,
+                                               ctypes.byref(foreign)), "dash_addr_metrics_from_events")
+    return rec, foreign.value
 
 
 def seed_schedule(seed: int, num_procs: int, rounds: int) -> np.ndarray:
@@ -907,6 +959,31 @@ class Engine:
         flags = cut if cut.size else np.zeros(1, dtype=np.uint8)
         _check(lib().dash_read_metrics(self.h, first, count, out.ctypes.data, flags.ctypes.data),
                "dash_read_metrics", self.h)
+        return rec, cut
+
+    def compute_addr_metrics(self) -> dict:
+        """dash_compute_addr_metrics: one GPU pass over the batch's event log of the last run (needs
+        trace_events), by address. Returns the totals: the first eleven ADDR_METRIC_FIELDS summed over all
+        records, msgs_max, foreign_events, class_addrs / class_misses / class_invalidations (lists of 5 in
+        ADDR_CLASS_NAMES' order), systems and truncated_systems. The records stay on the device for
+        read_addr_metrics until the next run."""
+        t = AddrTotals()
+        _check(lib().dash_compute_addr_metrics(self.h, ctypes.byref(t)), "dash_compute_addr_metrics", self.h)
+        return {f: [int(x) for x in getattr(t, f)] if f.startswith("class_") else int(getattr(t, f))
+                for f, _ in AddrTotals._fields_}
+
+    def read_addr_metrics(self, first=0, count=None):
+        """dash_read_addr_metrics: (records, truncated) of systems [first, first + count): a structured
+        array [count, num_procs * 16] with the ADDR_METRIC_FIELDS, indexed by address, and uint8 [count],
+        1 where the log was shorter than the system's run."""
+        count = self.num_systems - first if count is None else count
+        rec = np.zeros((max(count, 0), self.num_procs * MEM_SIZE), dtype=ADDR_METRICS_DTYPE)
+        cut = np.zeros(max(count, 0), dtype=np.uint8)
+        # a non-null pointer also for an empty window, whose range is still checked
+        out = rec if rec.size else np.zeros(1, dtype=ADDR_METRICS_DTYPE)
+        flags = cut if cut.size else np.zeros(1, dtype=np.uint8)
+        _check(lib().dash_read_addr_metrics(self.h, first, count, out.ctypes.data, flags.ctypes.data),
+               "dash_read_addr_metrics", self.h)
         return rec, cut
 
     def check_coherence(self) -> dict:
