@@ -230,6 +230,20 @@ int dash_set_micro_schedule(dash_t *h, const uint8_t *acts, uint32_t rounds);
    n == 0 returns the handle to its own seed and table. dash_set_system_seeds and
    dash_set_schedule replace each other: the last call wins. */
 int dash_set_system_seeds(dash_t *h, const uint64_t *seeds, uint64_t n);
+/* A delay word per system: lockstep but for up to four stated intervals in which one node sits out.
+   A delay is 16 bits, t | e << 3 | r << 6: node t (0..7) sits out the 1 << e rounds (e 0..7) from round
+   r (0..1022) on; 0xFFFF is an empty slot. A word holds four slots, slot s at bits 16 s, and the
+   all-ones word DASH_DELAY_LOCKSTEP is lockstep. Under word w node t sits out round q iff some
+   non-empty slot names t with r <= q < r + (1 << e); every other (round, node) is a lockstep step, the
+   node stepping and delivering at position t. Slots may overlap or repeat; a slot whose node is >=
+   num_procs has no effect. System k follows words[k], whichever queue-depth tiers it passes through.
+   Everything else is dash_set_system_seeds': the handle requirements and error codes, n ==
+   cfg.num_systems, words == NULL with n == 0 back to the handle's own seed and table, and the dash_set_*
+   call made last wins. dash_delay_schedule (below) writes a word's rounds as a dash_set_schedule table. */
+#define DASH_DELAY_EMPTY 0xFFFFu
+#define DASH_DELAY_LOCKSTEP 0xFFFFFFFFFFFFFFFFull
+#define DASH_DELAY(t, e, r) ((uint32_t)(t) | (uint32_t)(e) << 3 | (uint32_t)(r) << 6)
+int dash_set_system_delays(dash_t *h, const uint64_t *words, uint64_t n);
 /* After any successful load: every system becomes a copy of system src (trace rows and lengths,
    copied on the device). The handle stays loaded. */
 int dash_broadcast_system(dash_t *h, uint64_t src);
@@ -567,6 +581,38 @@ int dash_explore_sources(dash_t *h, uint64_t num_sources, uint64_t first_seed, u
                          uint64_t *n, dash_source_summary *per_source /* [num_sources] or NULL */,
                          dash_explore_totals *totals /* or NULL */);
 
+/* ---- every schedule within a few delays of lockstep (csrc/dash_delays.h) ----
+   A bounded schedule space that can be enumerated: lockstep plus at most max_delays delays (delay
+   words, dash_set_system_delays), each starting in one of the rounds 0 .. starts - 1 (starts 1..1023)
+   and 1, 2, .., 2^(lens - 1) rounds long (lens 1..8); max_delays is 0..4. The rule, stated once:
+
+   With N = num_procs and E = lens, cell c = (r * N + t) * E + e is the delay t | e << 3 | r << 6;
+   there are M = starts * N * E cells. The schedules with d delays have the indices [B_d, B_d + C(M, d)),
+   B_0 = 0, B_(d+1) = B_d + C(M, d), and K = B_(max_delays + 1) is the size of the space. Within a block
+   the rank j = index - B_d names the cells c_d > ... > c_1 by the combinatorial number system,
+   j = C(c_d, d) + ... + C(c_1, 1); slot s of the word holds cell c_(s+1) and the other slots are empty.
+   Index 0 is lockstep, and indices rise with the delay count: the lowest index that reaches an outcome
+   is a fewest-delays witness.
+
+   dash_delay_count gives K, dash_delay_word the word of index < K: DASH_EINVAL for space == NULL, a
+   field or num_procs outside the ranges above, index >= K, or a NULL result. Pure host code; the device
+   uses the same arithmetic (delay_unrank in csrc/dash_delays.h).
+
+   dash_explore_delays is dash_explore_sources (above) over this space: first_seed = 0,
+   seeds_per_source = K, weights == NULL, and the seed of a system is its schedule index, whose delay
+   word a kernel writes per system where dash_explore_sources writes the seed. Assignment, table, merge,
+   coherence records, the full-table rule (DASH_ETRUNC) and the handle's state afterwards (the words of
+   the last pass stay set, as after dash_set_system_delays) are that call's. out[k].o.seed is the lowest
+   index that reached the outcome, out[k].o.count how many schedules of the space reach it. Handle
+   requirements and error codes as dash_explore_sources, plus DASH_EINVAL for a space out of range. */
+typedef struct dash_delay_space { uint32_t starts, lens, max_delays, _reserved; } dash_delay_space;
+int dash_delay_count(const dash_delay_space *space, uint32_t num_procs, uint64_t *K);
+int dash_delay_word(const dash_delay_space *space, uint32_t num_procs, uint64_t index, uint64_t *word);
+int dash_explore_delays(dash_t *h, uint64_t num_sources, const dash_delay_space *space, uint64_t table_slots,
+                        dash_outcome_ex *out, uint64_t cap, uint64_t *n,
+                        dash_source_summary *per_source /* [num_sources] or NULL */,
+                        dash_explore_totals *totals /* or NULL */);
+
 /* ---- shrinking one system to a minimal reproducer (csrc/dash_shrink.hip) ----
    dash_check_coherence and the explores say that a system ends in a broken state, in 16 bytes.
    dash_shrink cuts the system down to a few instructions that still end in such a state: round by
@@ -727,6 +773,11 @@ int dash_probe_box(int device, dash_box_probe *out);
    the run's rounds reproduces the run; it can be read, edited and kept (tests/golden/schedules/).
    DASH_EINVAL for num_procs outside 1..8 or sched == NULL. */
 int dash_seed_schedule(uint64_t seed, uint32_t num_procs, uint32_t rounds, uint8_t *sched);
+/* Likewise the rounds [0, rounds) of a delay word (dash_set_system_delays): DASH_SIT_OUT where node t
+   sits the round out, else position t. Slots on nodes >= num_procs write nothing. A table that covers
+   the word's last interval reproduces the run (later rounds of a table are lockstep, as the word's
+   are). DASH_EINVAL for num_procs outside 1..8 or sched == NULL. */
+int dash_delay_schedule(uint64_t word, uint32_t num_procs, uint32_t rounds, uint8_t *sched);
 /* Which source and seed system k of a pass of dash_explore_sources runs, and whether its outcome is
    counted: the rule the device follows, stated once. A handle of S systems explores G sources
    (1 <= G <= S) with K seeds each, F the first seed (F + K must not wrap 2^64):

@@ -85,6 +85,17 @@
  *       classified on the GPU. Prints the outcome lines with a leading source-index column, ordered by
  *       (source, seed) (--coherence adds the same last column), then per source one line "source <i>
  *       <dir> outcomes=<n> schedules=<K> incoherent=<schedules whose final state breaks an invariant>"
+ *   --delays t@r+len[,t@r+len..]   lockstep but for up to four delays: node t sits out len rounds (1, 2,
+ *       .., 128) from round r (0..1022) on (dash_set_system_delays); "-" is lockstep itself. Writes the
+ *       dumps; --debug-instr, --debug-msg, --metrics, --addr-metrics and --coherence work as under --schedule;
+ *       e.g. `test_4 --delays 0@0+4,1@2+64`, the witness --explore-delays 2 prints for test_4's accepted
+ *       run_4, writes that run's dumps
+ *   --explore-delays D [--delay-starts R] [--delay-lens E]   every schedule within D (0..4) delays of
+ *       lockstep, start rounds 0 .. R - 1 (default: the rounds of the directory's own lockstep run, at most
+ *       1022) and lengths 1 .. 2^(E - 1) (default E = 7), enumerated and merged on the GPU
+ *       (dash_explore_delays). Prints the --explore lines, the seed column holding the lowest schedule index
+ *       that reached the outcome (a fewest-delays witness; --coherence adds its column), then that
+ *       witness's delays as --delays takes them. With --sources FILE as --explore with --sources
  *
  * Bulk modes (one GPU batch, many systems; dumps go to OUT_DIR/<k>/):
  *   --batch LIST        system k = the k-th trace directory listed in LIST (one per line)
@@ -324,13 +335,13 @@ static int print_coherence(dash_t *h) {
     return DASH_OK;
 }
 
-/* dash_simulate_dir plus a schedule (seed, explicit rounds, micro-steps, or a micro seed with its
-   weights) and the event log of the one system */
+/* dash_simulate_dir plus a schedule (seed, explicit rounds, micro-steps, a micro seed with its
+   weights, or a delay word) and the event log of the one system */
 static int simulate_traced(const char *dir, unsigned n, unsigned cs, unsigned m, const char *out, int dev,
                            int dbg_instr, int dbg_msg, unsigned long long sched, const uint8_t *rounds,
                            long nrounds, int micro, const uint64_t *mseed, uint64_t weights,
                            const char *write_micro_file, int metrics, int addr_metrics, int coherence,
-                           dash_stats *st) {
+                           const uint64_t *delays, dash_stats *st) {
     dash_cfg cfg = {0};
     cfg.num_procs = n;
     cfg.cache_size = cs;
@@ -343,13 +354,14 @@ static int simulate_traced(const char *dir, unsigned n, unsigned cs, unsigned m,
     uint64_t log_rounds = 1024u + 256ull * m;
     if (log_rounds > (1u << 22)) log_rounds = 1u << 22;
     cfg.trace_events = (dbg_instr || dbg_msg || write_micro_file || metrics || addr_metrics) ? (uint32_t)log_rounds : 0;
-    cfg.schedule_seed = (rounds || mseed) ? (sched ? sched : 1) : sched;
+    cfg.schedule_seed = (rounds || mseed || delays) ? (sched ? sched : 1) : sched;
     dash_t *h = NULL;
     int rc = dash_create(&cfg, &h);
     if (rc != DASH_OK) return rc;
     if (rounds) rc = micro ? dash_set_micro_schedule(h, rounds, (uint32_t)nrounds)
                            : dash_set_schedule(h, rounds, (uint32_t)nrounds);
     if (mseed) rc = dash_set_micro_seeds(h, mseed, &weights, 1);
+    if (delays) rc = dash_set_system_delays(h, delays, 1);
     if (rc == DASH_OK && (rc = dash_load_dir(h, dir, 0)) == DASH_OK && (rc = dash_run(h, st)) == DASH_OK) {
         dash_node_state nodes[DASH_MAX_PROCS];
         rc = dash_read_state(h, 0, nodes);
@@ -650,6 +662,101 @@ static int explore_sources_dirs(const char *dir, const char *list, unsigned n, u
     dash_destroy(h);
     batch_free(&b);
     dir_list_free(dirs, g);
+    return rc;
+}
+
+/* --delays SPEC: t@r+len[,t@r+len..], up to four delays "node t sits out len rounds from round r on" (len
+   a power of two up to 128, r up to 1022), or "-" for none, as a delay word (dash_set_system_delays) */
+static int parse_delays(const char *text, uint64_t *word) {
+    *word = DASH_DELAY_LOCKSTEP;
+    if (!strcmp(text, "-")) return 0;
+    for (unsigned s = 0; s < 4; s++) {
+        unsigned t, r, len, e = 0;
+        int used = 0;
+        if (sscanf(text, "%u@%u+%u%n", &t, &r, &len, &used) != 3 || t >= DASH_MAX_PROCS || r > 1022u) return -1;
+        while (e < 7 && (1u << e) < len) e++;
+        if (len != 1u << e) return -1;
+        *word = (*word & ~(0xFFFFull << (16 * s))) | (uint64_t)DASH_DELAY(t, e, r) << (16 * s);
+        text += used;
+        if (!*text) return 0;
+        if (*text++ != ',') return -1;
+    }
+    return -1; /* a fifth delay */
+}
+
+/* a delay word in --delays' own spelling */
+static void print_delays(uint64_t word) {
+    int any = 0;
+    for (unsigned s = 0; s < 4; s++) {
+        const unsigned f = (unsigned)(word >> (16 * s)) & 0xFFFFu;
+        if (f == DASH_DELAY_EMPTY) continue;
+        printf("%s%u@%u+%u", any ? "," : "", f & 7u, f >> 6, 1u << ((f >> 3) & 7u));
+        any = 1;
+    }
+    if (!any) printf("-");
+}
+
+/* --explore-delays D: the outcomes of every schedule within D delays of lockstep (dash_explore_delays) of
+   dir and, with --sources FILE, of the directories FILE lists. starts == 0: the rounds of dir's own lockstep
+   run, at most 1022. One line per outcome as --explore prints it (--sources: as with --sources), the seed
+   column being the witness's schedule index, then the witness's delays as --delays takes them. */
+static int explore_delays_dirs(const char *dir, const char *list, unsigned n, unsigned cs, unsigned m, int dev,
+                               unsigned max_delays, unsigned starts, unsigned lens, int coherence) {
+    char **dirs = NULL;
+    size_t g = 1;
+    int rc = DASH_OK;
+    if (list) rc = dir_list_read(dir, list, n, &dirs, &g);
+    if (list && !dirs) return rc;
+    const char *const *names = list ? (const char *const *)dirs : &dir;
+    batch b = {0};
+    dash_t *h = NULL;
+    dash_delay_space space = {starts, lens, max_delays, 0};
+    uint64_t K = 0;
+    if (rc == DASH_OK) rc = batch_parse(&b, names, g, n, m);
+    if (rc == DASH_OK && !starts) { /* the lockstep run of dir alone */
+        uint32_t rounds = 0;
+        const uint64_t none = DASH_DELAY_LOCKSTEP;
+        batch one = b;
+        one.nsys = 1;
+        if ((rc = batch_handle(&one, n, cs, m, dev, 1, 0, &h)) == DASH_OK &&
+            (rc = dash_set_system_delays(h, &none, 1)) == DASH_OK && (rc = dash_run(h, NULL)) == DASH_OK)
+            rc = dash_read_results(h, 0, 1, NULL, &rounds, NULL);
+        if (rc != DASH_OK && h) fprintf(stderr, "%s\n", dash_last_error(h));
+        dash_destroy(h);
+        h = NULL;
+        space.starts = rounds < 1 ? 1 : rounds > 1022 ? 1022 : rounds;
+    }
+    if (rc == DASH_OK && (rc = dash_delay_count(&space, n, &K)) != DASH_OK)
+        fprintf(stderr, "cache_simulator: --explore-delays: D 0..4, --delay-starts 1..1023, --delay-lens 1..8\n");
+    if (rc == DASH_OK) rc = batch_grow(&b, K < 65536 / g ? g * K : 65536, n);
+    if (rc == DASH_OK) rc = batch_handle(&b, n, cs, m, dev, 1, DASH_KEEP_STATE, &h);
+    if (rc == DASH_OK) {
+        uint64_t total = 0, cap = 4096;
+        dash_outcome_ex *o = NULL;
+        dash_source_summary *per = (dash_source_summary *)calloc(g, sizeof *per);
+        CALL_WITH_ROOM(rc, o, cap, total,
+                       per ? dash_explore_delays(h, g, &space, 0, o, cap, &total, per, NULL) : DASH_ENOMEM);
+        for (uint64_t i = 0; rc == DASH_OK && i < total && i < cap; i++) {
+            uint64_t word = DASH_DELAY_LOCKSTEP;
+            rc = dash_delay_word(&space, n, o[i].o.seed, &word);
+            if (list) printf("%u ", o[i].source);
+            printf("%016llx %llu %llu %u %x", (unsigned long long)o[i].o.digest, (unsigned long long)o[i].o.count,
+                   (unsigned long long)o[i].o.seed, o[i].o.rounds, o[i].o.errors);
+            if (coherence) printf(" %x", o[i].coh.bits);
+            printf(" ");
+            print_delays(word);
+            printf("\n");
+        }
+        for (size_t s = 0; list && rc == DASH_OK && s < g; s++)
+            printf("source %zu %s outcomes=%u schedules=%llu incoherent=%llu\n", s, names[s], per[s].outcomes,
+                   (unsigned long long)per[s].schedules, (unsigned long long)per[s].incoherent_schedules);
+        free(per);
+        free(o);
+    }
+    if (rc != DASH_OK && h) fprintf(stderr, "%s\n", dash_last_error(h));
+    dash_destroy(h);
+    batch_free(&b);
+    dir_list_free(dirs, list ? g : 0);
     return rc;
 }
 
@@ -975,7 +1082,10 @@ int main(int argc, char *argv[]) {
     uint32_t shrink_bits = 0;
     unsigned long long synth = 0, seed = 0x5EED, sched = 0, explore = 0, micro_seed = 0;
     int explore_given = 0, explore_micro = 0, micro_seed_given = 0, metrics = 0, addr_metrics = 0, coherence = 0;
-    uint64_t weights = DASH_MICRO_UNIFORM;
+    uint64_t weights = DASH_MICRO_UNIFORM, delay_word = DASH_DELAY_LOCKSTEP;
+    const char *delays_text = NULL;
+    unsigned explore_delays = 0, delay_starts = 0, delay_lens = 7;
+    int explore_delays_given = 0;
     unsigned len = 4096, kind = DASH_GEN_UNIFORM;
     double loc = 0.5;
     for (int i = 1; i < argc; i++) {
@@ -1007,6 +1117,11 @@ int main(int argc, char *argv[]) {
         else if (!strcmp(argv[i], "--micro-seed") && i + 1 < argc) micro_seed = strtoull(argv[++i], NULL, 0), micro_seed_given = 1;
         else if (!strcmp(argv[i], "--weights") && i + 1 < argc) weights_text = argv[++i];
         else if (!strcmp(argv[i], "--sources") && i + 1 < argc) sources_file = argv[++i];
+        else if (!strcmp(argv[i], "--delays") && i + 1 < argc) delays_text = argv[++i];
+        else if (!strcmp(argv[i], "--explore-delays") && i + 1 < argc)
+            explore_delays = (unsigned)strtoul(argv[++i], NULL, 0), explore_delays_given = 1;
+        else if (!strcmp(argv[i], "--delay-starts") && i + 1 < argc) delay_starts = (unsigned)strtoul(argv[++i], NULL, 0);
+        else if (!strcmp(argv[i], "--delay-lens") && i + 1 < argc) delay_lens = (unsigned)strtoul(argv[++i], NULL, 0);
         else if (!strcmp(argv[i], "--write-micro") && i + 1 < argc) write_micro_file = argv[++i];
         else if (!strcmp(argv[i], "--shrink") && i + 1 < argc) shrink_out = argv[++i];
         else if (!strcmp(argv[i], "--shrink-bits") && i + 1 < argc) shrink_bits = (uint32_t)strtoul(argv[++i], NULL, 0);
@@ -1033,6 +1148,8 @@ int main(int argc, char *argv[]) {
         fprintf(stderr, "       %s <test_directory> --coherence   coherence invariants of the final state\n", argv[0]);
         fprintf(stderr, "       %s <test_directory> --shrink OUTDIR   a minimal trace set with the same broken state\n", argv[0]);
         fprintf(stderr, "       %s <test_directory> --shrink OUTDIR --sources LIST   the same for many directories at once\n", argv[0]);
+        fprintf(stderr, "       %s <test_directory> --explore-delays D   every outcome within D delays of lockstep\n", argv[0]);
+        fprintf(stderr, "       %s <test_directory> --delays t@r+len[,..]   lockstep but node t sits out len rounds from r on\n", argv[0]);
         return EXIT_FAILURE;
     }
     if (weights_text && parse_weights(weights_text, n, &weights) != 0) {
@@ -1043,9 +1160,33 @@ int main(int argc, char *argv[]) {
         fprintf(stderr, "cache_simulator: --weights goes with --micro-seed or --explore-micro\n");
         return EXIT_FAILURE;
     }
-    if (sources_file && !explore_given && !shrink_out) {
-        fprintf(stderr, "cache_simulator: --sources goes with --explore, --explore-micro or --shrink\n");
+    if (sources_file && !explore_given && !shrink_out && !explore_delays_given) {
+        fprintf(stderr, "cache_simulator: --sources goes with --explore, --explore-micro, --explore-delays or --shrink\n");
         return EXIT_FAILURE;
+    }
+    if (delays_text && parse_delays(delays_text, &delay_word) != 0) {
+        fprintf(stderr, "cache_simulator: --delays: up to four t@r+len, node t 0..7, round r 0..1022, len 1, 2, .., 128\n");
+        return EXIT_FAILURE;
+    }
+    if ((delays_text || explore_delays_given) &&
+        (sched || rounds_file || micro_file || micro_seed_given || write_rounds_file || write_micro_file ||
+         explore_given || shrink_out || (delays_text && explore_delays_given))) {
+        fprintf(stderr, "cache_simulator: --delays and --explore-delays are schedules of their own: no --schedule, "
+                        "--rounds, --micro, --micro-seed, --write-rounds, --write-micro, --explore or --shrink\n");
+        return EXIT_FAILURE;
+    }
+    if (explore_delays_given) {
+        if (metrics || addr_metrics || dbg_instr || dbg_msg) {
+            fprintf(stderr, "cache_simulator: --explore-delays takes no --metrics, --addr-metrics or --debug-*\n");
+            return EXIT_FAILURE;
+        }
+        int rc = explore_delays_dirs(dir, sources_file, n, cs, m, dev, explore_delays, delay_starts, delay_lens,
+                                     coherence);
+        if (rc != DASH_OK) {
+            const char *why = dash_last_error(NULL);
+            fprintf(stderr, "cache_simulator: %s (%d)\n", why[0] ? why : "failed", rc);
+        }
+        return rc == DASH_OK ? EXIT_SUCCESS : EXIT_FAILURE;
     }
     if (shrink_bits && !shrink_out) {
         fprintf(stderr, "cache_simulator: --shrink-bits goes with --shrink\n");
@@ -1118,10 +1259,10 @@ int main(int argc, char *argv[]) {
     dash_stats st;
     const uint64_t mseed = micro_seed;
     int rc = (dbg_instr || dbg_msg || sched || rounds || write_rounds_file || micro_seed_given || metrics || addr_metrics ||
-              coherence)
+              coherence || delays_text)
                  ? simulate_traced(dir, n, cs, m, out, dev, dbg_instr, dbg_msg, sched, rounds, nrounds,
                                    micro_file != NULL, micro_seed_given ? &mseed : NULL, weights, write_micro_file,
-                                   metrics, addr_metrics, coherence, &st)
+                                   metrics, addr_metrics, coherence, delays_text ? &delay_word : NULL, &st)
                  : dash_simulate_dir(dir, n, cs, m, out, dev, &st);
     free(rounds);
     if (rc == DASH_OK && write_rounds_file &&

@@ -246,6 +246,11 @@ static dash::SimArgs sim_args(const dash_t* h) {
         break;
     case sched_src::system_seeds:
         a.arb_tab = reinterpret_cast<const uint32_t*>(h->d_seeds);
+        a.arb_seed = dash::ARB_SYSTEM_SEEDS;
+        break;
+    case sched_src::system_delays:  // the same buffer, holding delay words
+        a.arb_tab = reinterpret_cast<const uint32_t*>(h->d_seeds);
+        a.arb_seed = dash::ARB_SYSTEM_DELAYS;
         break;
     case sched_src::micro_seeds:  // (seed, weights) pairs
         a.arb_tab = reinterpret_cast<const uint32_t*>(h->d_mseeds);

@@ -63,7 +63,8 @@ struct SimArgs {
     uint32_t arb_len;         // a multiple of 4; rounds beyond it hash their key in the kernel
                               // (>= 4 for any table). 0: per-system seeds (dash_set_system_seeds),
                               // arb_tab points at uint64_t seeds[nsys] and arb_seed only selects
-                              // the seeded kernel
+                              // the seeded kernel and says what the words are: ARB_SYSTEM_SEEDS, or
+                              // ARB_SYSTEM_DELAYS for delay words (dash_set_system_delays)
     uint32_t micro;           // 1: arb_tab is a micro-step table (dash_set_micro_schedule, MODE 4); with
                               // arb_len == 0 (dash_set_micro_seeds) it points at uint64_t
                               // {seed, weights}[nsys], a seeded micro-step schedule per system
@@ -102,6 +103,8 @@ hipError_t launch_gen(const GenArgs& g, hipStream_t s);
 // the seeded schedule's table: each node's word (arb_node) of rounds [0, n), n a multiple of 4,
 // laid out [round / 4][node < seg][round % 4]; rounds past it are hashed in sim_kernel
 constexpr uint32_t ARB_TABLE_MAX = 1u << 22;
+// SimArgs.arb_seed of a round-schedule run with arb_len == 0: what the per-system words are
+constexpr uint64_t ARB_SYSTEM_SEEDS = 1, ARB_SYSTEM_DELAYS = 2;
 hipError_t launch_arb_table(uint64_t seed, uint32_t seg, uint32_t* out, uint32_t n, hipStream_t s);
 // skip[list[i]] = 1 for i < n
 // RD words carry value 0 (ref :839): clears bits 7..0 of every word whose bit 15 is 0

@@ -56,10 +56,13 @@ enum class sched_src : uint8_t {
     micro_table,   // d_arb holds a micro-step table (dash_set_micro_schedule, MODE 4)
     system_seeds,  // d_seeds: a seeded round schedule per system (dash_set_system_seeds)
     micro_seeds,   // d_mseeds: a seeded micro-step schedule per system (dash_set_micro_seeds)
+    system_delays, // d_seeds holds a delay word per system (dash_set_system_delays)
 };
 
 // a micro-step schedule (sim_kernel MODE 4): it runs at the reference's queue depth only
 inline bool micro_steps(sched_src s) { return s == sched_src::micro_table || s == sched_src::micro_seeds; }
+// a round schedule of its own per system, read from d_seeds: its runs made the overflow hint
+inline bool per_system_rounds(sched_src s) { return s == sched_src::system_seeds || s == sched_src::system_delays; }
 
 struct dash_ctx {
     dash_cfg cfg{};

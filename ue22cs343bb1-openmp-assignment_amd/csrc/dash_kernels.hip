@@ -31,6 +31,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "dash_delays.h"
 #include "dash_device.h"
 
 namespace dash {
@@ -140,6 +141,24 @@ __device__ __forceinline__ uint32_t arb_lane(uint64_t seed, uint32_t round, uint
     return (go + go) << (4u * pos);
 }
 
+// Node t's words of the four rounds from `round` on under a delay word that differs from lane to lane
+// (dash_set_system_delays; delay_sits in dash_delays.h states the rule): 0 where a non-empty slot names
+// t and covers the round, else the lockstep word, t stepping and delivering at position t. Built
+// arithmetically, as arb_lane's.
+__device__ __forceinline__ uint4 delay_lane(uint64_t word, uint32_t round, uint32_t t) {
+    uint32_t go[4] = {1u, 1u, 1u, 1u};
+#pragma unroll
+    for (uint32_t s = 0; s < DELAY_SLOTS; ++s) {
+        const uint32_t f = (uint32_t)(word >> (16u * s)) & 0xFFFFu;
+        const uint32_t mine = (f != DELAY_EMPTY ? 1u : 0u) & ((f & 7u) == t ? 1u : 0u);
+        const uint32_t off = round - (f >> 6), len = 1u << ((f >> 3) & 7u);  // unsigned: round < r wraps high
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) go[k] &= ~(mine & (off + k < len ? 1u : 0u));
+    }
+    return make_uint4((go[0] + go[0]) << (4u * t), (go[1] + go[1]) << (4u * t), (go[2] + go[2]) << (4u * t),
+                      (go[3] + go[3]) << (4u * t));
+}
+
 // The seeded micro-step schedule's pick (include/dash.h states the rule; host twin dash_micro_pick):
 // the node that acts in `round` of the system whose enabled nodes are the bits of `en` (all below
 // P), by the system's seed and weight bytes; the result is no node of the system when en == 0.
@@ -232,7 +251,8 @@ __device__ __forceinline__ mask_t Mbit15(uint32_t v) {
 //   1 = a seeded legal schedule (a.arb_seed != 0, DESIGN.md §2 -- per round, a node sits out
 //       with probability 1/4 and senders deliver in a seeded affine order; oracle twins
 //       orc_arb_stall, orc_arb_prio); with a.arb_len == 0 every system follows a seed of its own,
-//       hashed per lane at each trip start (dash_set_system_seeds; seed 0 = the lockstep rounds);
+//       hashed per lane at each trip start (dash_set_system_seeds; seed 0 = the lockstep rounds),
+//       or, with a.arb_seed == ARB_SYSTEM_DELAYS, a delay word of its own (dash_set_system_delays);
 //   2 = the DEBUG_MSG / DEBUG_INSTR event log (a.events) under lockstep;
 //   3 = the event log under a seeded (or explicit) schedule;
 //   4 = an explicit micro-step schedule with the event log (a.micro, dash_set_micro_schedule): per
@@ -998,8 +1018,11 @@ void sim_kernel(const SimArgs a) {
                 } else if (a.arb_len == 0u) {  // per-system seeds: a lane value, hashed on the vector unit
                     COLD();
                     const uint64_t sd = (uint64_t)arbn.x | ((uint64_t)arbn.y << 32);
-                    arbw = make_uint4(arb_lane(sd, rv, t, P), arb_lane(sd, rv + 1, t, P),
-                                      arb_lane(sd, rv + 2, t, P), arb_lane(sd, rv + 3, t, P));
+                    if (a.arb_seed == ARB_SYSTEM_DELAYS)  // or a delay word per system: no hash, four slot tests
+                        arbw = delay_lane(sd, rv, t);
+                    else
+                        arbw = make_uint4(arb_lane(sd, rv, t, P), arb_lane(sd, rv + 1, t, P),
+                                          arb_lane(sd, rv + 2, t, P), arb_lane(sd, rv + 3, t, P));
                 } else {
                     const uint32_t r0 = __builtin_amdgcn_readfirstlane(rv);
                     arbw = make_uint4(arb_node(arb_word(a.arb_seed, r0, P), t),

@@ -13,13 +13,15 @@ static_assert(offsetof(dash_outcome_ex, coh) == offsetof(dash::OutcomeOut, coh) 
                   offsetof(dash_outcome, rounds) == offsetof(dash::OutcomeOut, rounds),
               "field for field");
 
-extern "C" int dash_explore_sources(dash_t* h, uint64_t num_sources, uint64_t first_seed, uint64_t seeds_per_source,
-                                    const uint64_t* weights, uint64_t table_slots, dash_outcome_ex* out, uint64_t cap,
-                                    uint64_t* n, dash_source_summary* per_source, dash_explore_totals* totals) {
-    return guarded(h, "dash_explore_sources", [&]() -> int {
+// dash_explore_sources, and with `delays` dash_explore_delays: the seed of a system is then its schedule
+// index in that space and the pass's fill kernel writes the index's delay word where it would write the seed
+static int explore_sources(dash_t* h, const char* what, uint64_t num_sources, uint64_t first_seed,
+                           uint64_t seeds_per_source, const uint64_t* weights, const dash::DelaySpace* delays,
+                           uint64_t table_slots, dash_outcome_ex* out, uint64_t cap, uint64_t* n,
+                           dash_source_summary* per_source, dash_explore_totals* totals) {
+    return guarded(h, what, [&]() -> int {
         if (!h || !n || (!out && cap)) return DASH_EINVAL;
         *n = 0;
-        const char* what = "dash_explore_sources";
         const uint64_t S = h->cfg.num_systems, G = num_sources, K = seeds_per_source, F = first_seed;
         if (!h->d_arb) return fail(h, DASH_ESTATE, "%s: handle created with schedule_seed = 0", what);
         if (!h->d_state) return fail(h, DASH_ESTATE, "%s: created without DASH_KEEP_STATE", what);
@@ -52,7 +54,9 @@ extern "C" int dash_explore_sources(dash_t* h, uint64_t num_sources, uint64_t fi
         uint64_t* const d_seeds = weights ? h->d_mseeds : h->d_seeds;
 
         double sim_ms = 0, merge_ms = 0, insert_ms = 0;
-        const sched_src src = weights ? sched_src::micro_seeds : sched_src::system_seeds;
+        const sched_src src = weights  ? sched_src::micro_seeds
+                              : delays ? sched_src::system_delays
+                                       : sched_src::system_seeds;
         // before the first pass: the copies of the sources and an empty table
         HIPCHK(h, timer.mark(0, h->stream));
         HIPCHK(h, dash::launch_replicate(h->d_trace, h->d_lens, S, G, (uint64_t)h->seg * h->nchunks, h->cfg.num_procs,
@@ -62,10 +66,14 @@ extern "C" int dash_explore_sources(dash_t* h, uint64_t num_sources, uint64_t fi
         for (uint64_t p = 0; p < passes; p++) {
             const dash::AssignArgs a{S, G, K, F, R, p * R};
             if (p) HIPCHK(h, timer.mark(0, h->stream));
-            HIPCHK(h, dash::launch_fill_seeds(d_seeds, a, weights ? 1u : 0u, weights ? *weights : 0, h->stream));
+            if (delays)
+                HIPCHK(h, dash::launch_fill_delays(d_seeds, a, *delays, h->stream));
+            else
+                HIPCHK(h, dash::launch_fill_seeds(d_seeds, a, weights ? 1u : 0u, weights ? *weights : 0, h->stream));
             HIPCHK(h, timer.mark(1, h->stream));
-            // the handle now follows per-system seeds, as dash_set_system_seeds / dash_set_micro_seeds
-            // leave it (the kernels above run before dash_run's on the same stream)
+            // the handle now follows per-system seeds (or delay words), as dash_set_system_seeds /
+            // dash_set_micro_seeds / dash_set_system_delays leave it (the kernels above run before
+            // dash_run's on the same stream)
             if ((rc = run_pass(h, &src, sim_ms)) != DASH_OK) return rc;
             HIPCHK(h, timer.add(0, 1, merge_ms));
             if (p) {  // the previous pass's merge
@@ -149,4 +157,23 @@ extern "C" int dash_explore_sources(dash_t* h, uint64_t num_sources, uint64_t fi
                         (unsigned long long)slots, (unsigned long long)t.unplaced);
         return DASH_OK;
     });
+}
+
+extern "C" int dash_explore_sources(dash_t* h, uint64_t num_sources, uint64_t first_seed, uint64_t seeds_per_source,
+                                    const uint64_t* weights, uint64_t table_slots, dash_outcome_ex* out, uint64_t cap,
+                                    uint64_t* n, dash_source_summary* per_source, dash_explore_totals* totals) {
+    return explore_sources(h, "dash_explore_sources", num_sources, first_seed, seeds_per_source, weights, nullptr,
+                           table_slots, out, cap, n, per_source, totals);
+}
+
+extern "C" int dash_explore_delays(dash_t* h, uint64_t num_sources, const dash_delay_space* space, uint64_t table_slots,
+                                   dash_outcome_ex* out, uint64_t cap, uint64_t* n, dash_source_summary* per_source,
+                                   dash_explore_totals* totals) {
+    if (!h || !n || (!out && cap)) return DASH_EINVAL;
+    *n = 0;
+    dash::DelaySpace s{};
+    if (space) s = dash::DelaySpace{space->starts, space->lens, space->max_delays, h->cfg.num_procs};
+    if (!space || !dash::delay_space_valid(s)) return fail(h, DASH_EINVAL, "dash_explore_delays: space out of range");
+    return explore_sources(h, "dash_explore_delays", num_sources, 0, dash::delay_count(s), nullptr, &s, table_slots,
+                           out, cap, n, per_source, totals);
 }

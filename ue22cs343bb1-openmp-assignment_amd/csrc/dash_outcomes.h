@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dash_delays.h"
+
 namespace dash {
 
 // One pass of dash_explore_assign (include/dash.h) for the kernels: S systems, G sources, K seeds per
@@ -51,6 +53,9 @@ hipError_t launch_replicate(uint2* trace, uint32_t* lens, uint64_t nsys, uint64_
                             hipStream_t s);
 // the pass's seeds: seeds[k] (pairs == 0) or seeds[2 * k], seeds[2 * k + 1] = seed, weights
 hipError_t launch_fill_seeds(uint64_t* seeds, const AssignArgs& a, uint32_t pairs, uint64_t weights, hipStream_t s);
+// dash_explore_delays: words[k] = the delay word of system k's seed, a schedule index of `space`
+// (delay_unrank, dash_delays.h); a.F == 0 and a.K == delay_count(space)
+hipError_t launch_fill_delays(uint64_t* words, const AssignArgs& a, const DelaySpace& space, hipStream_t s);
 hipError_t launch_clear_table(OutcomeSlot* table, uint64_t slots, unsigned long long* counters, hipStream_t s);
 // every counted system of the pass into the table; place[k] = its slot or NOT_PLACED. group_keys: as
 // GROUP_KEYS (0 = every lane for itself, 64 = groups only)

@@ -5,7 +5,8 @@
 // Per call:  replicate, clear_table;  per pass:  fill_seeds, [dash_run], insert, [the coherence
 // launch], witness;  at the end:  compact. All on the handle's stream, one thread per system (or per
 // slot). dash_explore_assign (csrc/dash_host.c) states the pass assignment once; assign() below is
-// its twin, and fill_seeds, insert and witness all go through it.
+// its twin, and fill_seeds, insert and witness all go through it. dash_explore_delays is the same call
+// with fill_delays in place of fill_seeds: the seed is a schedule index, the system follows its delay word.
 //
 // The table is open addressing with linear probing over a power-of-two number of 64-B slots
 // (OutcomeSlot, dash_outcomes.h). There is no 128-bit compare-and-swap, so a key is two words, each
@@ -111,6 +112,17 @@ __global__ __launch_bounds__(THREADS) void fill_seeds_kernel(uint64_t* seeds, As
     } else {
         seeds[k] = seed;
     }
+}
+
+// fill_seeds for dash_explore_delays: the system's seed is a schedule index, and what it follows is that
+// index's delay word
+__global__ __launch_bounds__(THREADS) void fill_delays_kernel(uint64_t* words, AssignArgs a, DelaySpace space) {
+    const uint64_t k = (uint64_t)blockIdx.x * THREADS + threadIdx.x;
+    if (k >= a.S) return;
+    uint64_t source, index;
+    bool counted;
+    assign(a, k, source, index, counted);
+    words[k] = delay_unrank(space, index);  // index < a.K = delay_count(space): counted or a repeat of one that is
 }
 
 __global__ __launch_bounds__(THREADS) void clear_table_kernel(OutcomeSlot* table, uint64_t slots,
@@ -237,6 +249,14 @@ hipError_t launch_fill_seeds(uint64_t* seeds, const AssignArgs& a, uint32_t pair
     uint32_t blocks;
     if (hipError_t e = grid_for(a.S, blocks)) return e;
     hipLaunchKernelGGL(fill_seeds_kernel, dim3(blocks), dim3(THREADS), 0, s, seeds, a, pairs, weights);
+    return hipGetLastError();
+}
+
+hipError_t launch_fill_delays(uint64_t* words, const AssignArgs& a, const DelaySpace& space, hipStream_t s) {
+    if (!delay_space_valid(space) || a.F != 0 || a.K != delay_count(space) || a.base >= a.K) return hipErrorInvalidValue;
+    uint32_t blocks;
+    if (hipError_t e = grid_for(a.S, blocks)) return e;
+    hipLaunchKernelGGL(fill_delays_kernel, dim3(blocks), dim3(THREADS), 0, s, words, a, space);
     return hipGetLastError();
 }
 

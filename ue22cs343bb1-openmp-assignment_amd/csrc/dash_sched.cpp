@@ -6,6 +6,7 @@
 // (tab_explicit); going back to the handle's seed rebuilds it.
 #include <map>
 
+#include "dash_delays.h"
 #include "dash_internal.h"
 
 // every schedule call needs a handle created with a schedule seed (it owns the round table)
@@ -129,12 +130,56 @@ int dash_set_system_seeds(dash_t* h, const uint64_t* seeds, uint64_t n) {
             return fail(h, DASH_ESTATE, "dash_set_system_seeds: the handle follows a micro-step schedule");
         HIPCHK(h, hipSetDevice(h->cfg.device));
         // leaving the seeds voids the hint they made; a round table's own hint still stands
-        if (!seeds) return unset_seeds(h, "dash_set_system_seeds", n, h->follow == sched_src::system_seeds);
+        if (!seeds) return unset_seeds(h, "dash_set_system_seeds", n, per_system_rounds(h->follow));
         if (n != h->cfg.num_systems)
             return fail(h, DASH_EINVAL, "dash_set_system_seeds: %llu seeds for %llu systems", (unsigned long long)n,
                         (unsigned long long)h->cfg.num_systems);
         return upload_seeds(h, seeds, n, sched_src::system_seeds);
     });
+}
+
+int dash_set_system_delays(dash_t* h, const uint64_t* words, uint64_t n) {
+    return guarded(h, "dash_set_system_delays", [&]() -> int {
+        if (!h) return DASH_EINVAL;
+        if (int rc = need_seed(h, "dash_set_system_delays")) return rc;
+        if (h->follow == sched_src::micro_table)
+            return fail(h, DASH_ESTATE, "dash_set_system_delays: the handle follows a micro-step schedule");
+        HIPCHK(h, hipSetDevice(h->cfg.device));
+        if (!words) return unset_seeds(h, "dash_set_system_delays", n, per_system_rounds(h->follow));
+        if (n != h->cfg.num_systems)
+            return fail(h, DASH_EINVAL, "dash_set_system_delays: %llu words for %llu systems", (unsigned long long)n,
+                        (unsigned long long)h->cfg.num_systems);
+        return upload_seeds(h, words, n, sched_src::system_delays);  // the words ride in the seed buffer
+    });
+}
+
+int dash_delay_schedule(uint64_t word, uint32_t num_procs, uint32_t rounds, uint8_t* sched) {
+    if (num_procs < 1 || num_procs > DASH_MAX_PROCS || !sched) return DASH_EINVAL;
+    for (uint64_t r = 0; r < rounds; r++)
+        for (uint32_t t = 0; t < num_procs; t++)
+            sched[r * num_procs + t] = dash::delay_sits(word, t, (uint32_t)r) ? (uint8_t)DASH_SIT_OUT : (uint8_t)t;
+    return DASH_OK;
+}
+
+// a dash_delay_space over num_procs nodes as the shared arithmetic takes it; false when out of range
+static bool delay_space_of(const dash_delay_space* sp, uint32_t num_procs, dash::DelaySpace& out) {
+    if (!sp) return false;
+    out = dash::DelaySpace{sp->starts, sp->lens, sp->max_delays, num_procs};
+    return dash::delay_space_valid(out);
+}
+
+int dash_delay_count(const dash_delay_space* space, uint32_t num_procs, uint64_t* K) {
+    dash::DelaySpace s;
+    if (!K || !delay_space_of(space, num_procs, s)) return DASH_EINVAL;
+    *K = dash::delay_count(s);
+    return DASH_OK;
+}
+
+int dash_delay_word(const dash_delay_space* space, uint32_t num_procs, uint64_t index, uint64_t* word) {
+    dash::DelaySpace s;
+    if (!word || !delay_space_of(space, num_procs, s) || index >= dash::delay_count(s)) return DASH_EINVAL;
+    *word = dash::delay_unrank(s, index);
+    return DASH_OK;
 }
 
 int dash_set_micro_seeds(dash_t* h, const uint64_t* seeds, const uint64_t* weights, uint64_t n) {

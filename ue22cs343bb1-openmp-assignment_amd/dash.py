@@ -17,6 +17,9 @@ libdash:
     Engine.explore_sources(g, s0, k) -> the outcomes of g trace sets at once, merged and classified on
                                       the GPU (counts, witnesses, coherence records; explore_assign
                                       states which system runs which source and seed)
+    Engine.explore_delays(g, R, E, D) -> the same over every schedule within D delays of lockstep
+                                      (delay_count, delay_word and delay_schedule state the space;
+                                      set_system_delays runs chosen delay words)
     Engine.shrink_many(jobs)       -> many (system, seed, goal) jobs shrunk side by side in one call, each
                                       to where Engine.shrink takes it alone (shrink_assign states how
                                       a sub-pass's systems are dealt out)
@@ -88,7 +91,9 @@ EXPORTS = ("dash_create", "dash_destroy", "dash_last_error", "dash_load_traces",
            "dash_check_outcomes", "dash_explore_sources", "dash_explore_assign", "dash_shrink",
            "dash_shrink_candidate", "dash_write_dir", "dash_test_write_states", "dash_shrink_many",
            "dash_shrink_assign", "dash_compute_addr_metrics", "dash_read_addr_metrics", "dash_addr_class",
-           "dash_addr_metrics_from_events")
+           "dash_addr_metrics_from_events", "dash_set_system_delays", "dash_delay_schedule", "dash_delay_count",
+           "dash_delay_word", "dash_explore_delays")
+DELAY_EMPTY, DELAY_LOCKSTEP = 0xFFFF, 0xFFFFFFFFFFFFFFFF  # DASH_DELAY_EMPTY, DASH_DELAY_LOCKSTEP
 TEXT_TILE = 4096  # DASH_TEXT_TILE: bytes per tile of the device text parser
 SIT_OUT = 0xFF
 MICRO_STEP, MICRO_SEND = 0, 1  # dash_set_micro_schedule actions
@@ -235,6 +240,11 @@ class ExploreTotals(ctypes.Structure):
         return d
 
 
+# dash_delay_space (dash_delay_count, dash_delay_word, dash_explore_delays)
+class DelaySpace(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint32) for f in ("starts", "lens", "max_delays", "_reserved")]
+
+
 # dash_shrink_goal / dash_shrink_step / dash_shrink_report (dash_shrink)
 class ShrinkGoal(ctypes.Structure):
     _fields_ = [(f, ctypes.c_uint32) for f in ("coh_all", "err_all", "err_none", "_reserved")]
@@ -359,6 +369,12 @@ def lib() -> ctypes.CDLL:
         "dash_read_addr_metrics": (i32, [vp, u64, u64, vp, vp]),
         "dash_addr_class": (i32, [ctypes.POINTER(AddrMetrics)]),
         "dash_addr_metrics_from_events": (i32, [vp, u64, u32, u32, vp, ctypes.POINTER(u64)]),
+        "dash_set_system_delays": (i32, [vp, vp, u64]),
+        "dash_delay_schedule": (i32, [u64, u32, u32, vp]),
+        "dash_delay_count": (i32, [ctypes.POINTER(DelaySpace), u32, ctypes.POINTER(u64)]),
+        "dash_delay_word": (i32, [ctypes.POINTER(DelaySpace), u32, u64, ctypes.POINTER(u64)]),
+        "dash_explore_delays": (i32, [vp, u64, ctypes.POINTER(DelaySpace), u64, vp, u64, ctypes.POINTER(u64), vp,
+                                      ctypes.POINTER(ExploreTotals)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -518,6 +534,66 @@ def seed_schedule(seed: int, num_procs: int, rounds: int) -> np.ndarray:
     # a zero-round table still needs a non-null pointer
     buf = sched if rounds and num_procs else np.zeros(1, dtype=np.uint8)
     _check(lib().dash_seed_schedule(seed, num_procs, rounds, buf.ctypes.data), "dash_seed_schedule")
+    return sched
+
+
+def delay_pack(delays) -> int:
+    """A delay word (dash_set_system_delays) from up to four (node, start, length) delays: node 0..7,
+    start round 0..1022, length a power of two 1..128; slot s holds delays[s], the others are empty."""
+    delays = list(delays)
+    if len(delays) > 4:
+        raise ValueError("delay_pack: at most four delays")
+    word = DELAY_LOCKSTEP
+    for s, (t, r, length) in enumerate(delays):
+        t, r, length = int(t), int(r), int(length)
+        e = length.bit_length() - 1
+        if not (0 <= t < 8 and 0 <= r <= 1022 and 1 <= length <= 128 and length == 1 << e):
+            raise ValueError(f"delay_pack: delay {(t, r, length)} out of range")
+        word = word & ~(0xFFFF << (16 * s)) | (t | e << 3 | r << 6) << (16 * s)
+    return word
+
+
+def delay_unpack(word: int) -> list:
+    """The non-empty slots of a delay word as (node, start, length), in slot order."""
+    slots = [(int(word) >> (16 * s)) & 0xFFFF for s in range(4)]
+    return [(f & 7, f >> 6, 1 << ((f >> 3) & 7)) for f in slots if f != DELAY_EMPTY]
+
+
+def delay_format(word: int) -> str:
+    """A delay word in the CLI's spelling, t@r+len[,t@r+len..] (cache_simulator --delays); lockstep is ''."""
+    return ",".join(f"{t}@{r}+{n}" for t, r, n in delay_unpack(word))
+
+
+def _delay_space(starts: int, lens: int, max_delays: int) -> DelaySpace:
+    if min(starts, lens, max_delays) < 0 or max(starts, lens, max_delays) > 0xFFFFFFFF:
+        raise DashError(EINVAL, "dash_delay_space")
+    return DelaySpace(starts, lens, max_delays, 0)
+
+
+def delay_count(starts: int, lens: int, max_delays: int, num_procs: int) -> int:
+    """dash_delay_count: K, the schedules of the space lockstep + at most max_delays delays with start
+    rounds 0 .. starts - 1 and lengths 1 .. 2^(lens - 1), over num_procs nodes."""
+    K = ctypes.c_uint64()
+    _check(lib().dash_delay_count(ctypes.byref(_delay_space(starts, lens, max_delays)), num_procs, ctypes.byref(K)),
+           "dash_delay_count")
+    return K.value
+
+
+def delay_word(starts: int, lens: int, max_delays: int, num_procs: int, index: int) -> int:
+    """dash_delay_word: the delay word of schedule `index` < delay_count(...) (index 0 is lockstep,
+    indices rise with the delay count)."""
+    w = ctypes.c_uint64()
+    _check(lib().dash_delay_word(ctypes.byref(_delay_space(starts, lens, max_delays)), num_procs, index,
+                                 ctypes.byref(w)), "dash_delay_word")
+    return w.value
+
+
+def delay_schedule(word: int, num_procs: int, rounds: int) -> np.ndarray:
+    """dash_delay_schedule: the rounds [0, rounds) of a delay word as a set_schedule table, uint8
+    [rounds][num_procs] of SIT_OUT or the node's own position."""
+    sched = np.zeros((rounds, num_procs), dtype=np.uint8)
+    buf = sched if rounds and num_procs else np.zeros(1, dtype=np.uint8)
+    _check(lib().dash_delay_schedule(word, num_procs, rounds, buf.ctypes.data), "dash_delay_schedule")
     return sched
 
 
@@ -751,6 +827,16 @@ class Engine:
         assert seeds.ndim == 1
         _check(lib().dash_set_system_seeds(self.h, seeds.ctypes.data, len(seeds)), "dash_set_system_seeds", self.h)
 
+    def set_system_delays(self, words):
+        """dash_set_system_delays: system k follows the delay word words[k] (delay_pack; DELAY_LOCKSTEP
+        = lockstep); None returns the handle to its own seed. Needs schedule_seed != 0."""
+        if words is None:
+            _check(lib().dash_set_system_delays(self.h, None, 0), "dash_set_system_delays", self.h)
+            return
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        assert words.ndim == 1
+        _check(lib().dash_set_system_delays(self.h, words.ctypes.data, len(words)), "dash_set_system_delays", self.h)
+
     def set_micro_seeds(self, seeds, weights=None, weights_per_system=None):
         """dash_set_micro_seeds: system k follows the seeded micro-step schedule of seeds[k] under
         its weight vector. weights: one vector for every system, a sequence of per-node weights or a
@@ -826,21 +912,36 @@ class Engine:
         there before DashError(ETRUNC) is raised."""
         want = min(max(num_sources * seeds_per_source, 1), 1 << 22) if cap is None else cap
         w = None if weights is None else ctypes.byref(ctypes.c_uint64(pack_weights(weights)))
+        fn = lib().dash_explore_sources
+        return self._explore_sources("dash_explore_sources", num_sources, want, cap, lambda *res: fn(
+            self.h, num_sources, first_seed, seeds_per_source, w, table_slots, *res))
+
+    def explore_delays(self, num_sources: int, starts: int, lens: int, max_delays: int, table_slots=0, cap=None):
+        """dash_explore_delays: explore_sources over every schedule within max_delays delays of lockstep
+        (start rounds 0 .. starts - 1, lengths 1 .. 2^(lens - 1); delay_count gives their number). The
+        outcomes' seed is the lowest schedule index that reached them, a fewest-delays witness:
+        delay_word turns it into the delay word, delay_unpack into (node, start, length). The result is
+        explore_sources' and stays on the engine the same way."""
+        space = _delay_space(starts, lens, max_delays)
+        want = 4096 if cap is None else cap
+        fn = lib().dash_explore_delays
+        return self._explore_sources("dash_explore_delays", num_sources, want, cap, lambda *res: fn(
+            self.h, num_sources, ctypes.byref(space), table_slots, *res))
+
+    def _explore_sources(self, what, num_sources, want, cap, call):
         per = np.zeros(max(num_sources, 0), dtype=SOURCE_SUMMARY_DTYPE)
         per_buf = per if per.size else np.zeros(1, dtype=SOURCE_SUMMARY_DTYPE)
         while True:
             outs = np.zeros(max(want, 1), dtype=OUTCOME_EX_DTYPE)
             tot, n = ExploreTotals(), ctypes.c_uint64()
-            rc = lib().dash_explore_sources(self.h, num_sources, first_seed, seeds_per_source, w, table_slots,
-                                            outs.ctypes.data, want, ctypes.byref(n), per_buf.ctypes.data,
-                                            ctypes.byref(tot))
+            rc = call(outs.ctypes.data, want, ctypes.byref(n), per_buf.ctypes.data, ctypes.byref(tot))
             if rc not in (OK, ETRUNC) or cap is not None or n.value <= want:
                 break
             want = n.value  # more outcomes than the first guess held: once more, with room for all
         if rc in (OK, ETRUNC):
             self.explore_total = int(n.value)
             self.explore_sources_result = (outs[:min(n.value, want)], per, tot.as_dict())
-        _check(rc, "dash_explore_sources", self.h)
+        _check(rc, what, self.h)
         return self.explore_sources_result
 
     def shrink(self, src: int, coh_all: int, err_all=0, err_none=0xFFFFFFFF, seed=0, cap=None) -> dict:
